@@ -15,14 +15,20 @@ rounding noise).
        with max_chi = 64 truncation, sort back at save) and take 1 - |<0|psi>|^2.
 value = (S * 1225 + S * 4) evaluations / step time (max over ranks): weak scaling.
 
-Also reported (outside the timed region):
+A plain run sets up, warms up, times ``--steps`` steps and prints the result line (with the
+per-family kernel times the library's timers collected during those steps, HIP events on the MPS
+stream around every launch, and the dominant kernel's roofline worked out from them).
+``--dump-outputs DIR`` also writes what the last timed step returned -- the gradient scores, the
+per-state best pair and the overlap costs -- as ``DIR/<name>.npy`` (float64); the inputs are
+seeded, so two builds can be compared output for output.
+
+With ``--full`` also reported (outside the timed region):
   * each evaluation kind timed on its own (gradient / overlap evals per second) and the rate at
     the reference's own per-layer mix (1225 gradients + 113 Rotoselect overlap evaluations);
   * ``parity_check``: one state's 1225 gradients and arg-max pair and four overlap evaluations
     (one per distance, through the fused chain) against the oracle;
   * ``latency``: one state alone -- one overlap evaluation per distance, and one Rotoselect gate
     (``replace_with_best_1q_gate``'s 7 evaluations) on the cached-prefix path;
-  * the dominant kernel's roofline (HIP events on the MPS stream around every launch);
   * CPU baselines: the oracle's port of the reference algorithm (per-pair, per-generator MPS
     build + whole-psi dot; numpy LAPACK SVDs), one process per host core with single-threaded
     BLAS, on a bounded sample, run on rank 0 at N = 1 before the GPU is touched.
@@ -316,6 +322,22 @@ def cpu_baselines(budget_s, workers):
     return out
 
 
+DUMP_MAX_BYTES = 16 << 20  # per dumped array (three arrays: well under 64 MB in all)
+
+
+def dump_outputs(out_dir, rank, world, arrays):
+    """Write what the last timed step returned as out_dir/<name>.npy (float64; device tensors are
+    copied to the host).  With more than one rank every rank writes its own <name>_rank<r>.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if hasattr(a, "detach"):
+            a = a.detach().cpu().numpy()
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.nbytes > DUMP_MAX_BYTES:  # a larger batch than the default: its leading rows
+            a = a[: max(1, DUMP_MAX_BYTES // (a.nbytes // len(a)))]
+        np.save(os.path.join(out_dir, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a)
+
+
 # ---------------------------------------------------------------------------------------------
 def main():
     ap = argparse.ArgumentParser()
@@ -325,12 +347,17 @@ def main():
     ap.add_argument("--states", type=int, default=256, help="states per rank")
     ap.add_argument("--distinct", type=int, default=8, help="distinct synthetic states generated")
     ap.add_argument("--state-kind", default="near-product", choices=("near-product", "random"))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (scores, best pairs, overlap costs) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baselines, each evaluation kind on its own, the parity check against the "
+                         "oracle and the single-state latencies")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--cpu-budget", type=float, default=4.0, help="seconds per CPU-baseline leg")
     ap.add_argument("--cpu-workers", type=int, default=0, help="0: min(16, OMP_NUM_THREADS or cores)")
     ap.add_argument("--cpu-settle", type=float, default=0.0, help="seconds of idle after the CPU-baseline leg")
-    ap.add_argument("--no-parity", action="store_true")
-    ap.add_argument("--no-latency", action="store_true")
+    ap.add_argument("--no-parity", action="store_true", help="--full without the parity check")
+    ap.add_argument("--no-latency", action="store_true", help="--full without the latency block")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="sweep, then the overlap evaluations with a flag check after the chain (no overlap of host work)")
     ap.add_argument("--simulate-world", type=int, default=0,
@@ -344,6 +371,8 @@ def main():
                     help="config 4 strong scaling: a fixed global batch of chi=128 sweeps sharded by state")
     ap.add_argument("--global-states", type=int, default=512, help="--strong: sweeps in the global batch")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.strong:
         return strong_main(args)
 
@@ -353,7 +382,7 @@ def main():
     os.environ["AQC_DEVICE"] = str(local)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.simulate_world:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.simulate_world:
         workers = args.cpu_workers or min(16, int(os.environ.get("OMP_NUM_THREADS", os.cpu_count() or 1)))
         cpu = cpu_baselines(args.cpu_budget, workers)
         cpu["workers"] = workers
@@ -516,15 +545,25 @@ def main():
     fams = {f: _lib.timing_query(f)
             for f in ("mps_chain", "mps_svd", "mps_theta", "mps_split", "grad_chain", "mps_overlap0", "mps_copy")}
 
-    # each evaluation kind on its own (outside the headline timed region)
-    k_ph = max(2, args.steps // 2)
-    t_sw, _ = timed(sweep, k_ph)
-    t_ov, _ = timed(overlaps, k_ph)
-    grad_rate = S * len(cmap) * k_ph / t_sw
-    ov_rate = B * len(DISTANCES) * k_ph / t_ov * (shard_world if not sim else 1)
-    mix_g, mix_o = len(cmap), REF_OVERLAPS_PER_LAYER
-    ref_mix = (mix_g + mix_o) / (mix_g / grad_rate + mix_o / ov_rate)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world,
+                     {"pair_scores": full, "best_pair": best, "overlap_costs": costs})
 
+    by_kind = None
+    if args.full:
+        # each evaluation kind on its own (outside the headline timed region)
+        k_ph = max(2, args.steps // 2)
+        t_sw, _ = timed(sweep, k_ph)
+        t_ov, _ = timed(overlaps, k_ph)
+        grad_rate = S * len(cmap) * k_ph / t_sw
+        ov_rate = B * len(DISTANCES) * k_ph / t_ov * (shard_world if not sim else 1)
+        mix_g, mix_o = len(cmap), REF_OVERLAPS_PER_LAYER
+        ref_mix = (mix_g + mix_o) / (mix_g / grad_rate + mix_o / ov_rate)
+        by_kind = {"gradient_evals_per_s": grad_rate, "overlap_evals_per_s": ov_rate,
+                   "reference_mix_evals_per_s": ref_mix,
+                   "reference_mix": f"{mix_g} gradients + {mix_o} overlap evals per state (one layer, SURVEY 3 S2)"}
+
+    # the dominant kernel's roofline, from the library's timers over the timed steps (no run of its own)
     dom = max(fams, key=lambda f: fams[f]["ms"])
     fd = fams[dom]
     launches = max(fd["launches"], 1)
@@ -581,10 +620,10 @@ def main():
     roof["launches"] = fd["launches"]
 
     parity = None
-    if rank == 0 and not args.no_parity and not sim:
+    if args.full and rank == 0 and not args.no_parity and not sim:
         parity = parity_check(full, best, costs, distinct, layer_angles, shard_world, cmap, prio)
     latency = None
-    if rank == 0 and world == 1 and not args.no_latency and not sim:
+    if args.full and rank == 0 and world == 1 and not args.no_latency and not sim:
         latency = latency_block(distinct[0], cpu)
 
     if rank == 0 and sim:
@@ -652,25 +691,19 @@ def main():
             },
             "breakdown_ms": {f: round(v["ms"] / args.steps, 3) for f, v in fams.items()},
             "step_ms": [round(1e3 * (b - a), 3) for a, b in zip([0.0] + main_step_s[:-1], main_step_s)],
-            "by_kind": {
-                "gradient_evals_per_s": grad_rate, "overlap_evals_per_s": ov_rate,
-                "reference_mix_evals_per_s": ref_mix,
-                "reference_mix": f"{mix_g} gradients + {mix_o} overlap evals per state (one layer, SURVEY 3 S2)",
-                "vs_cpu": ({"gradient": grad_rate / cpu_line["gradient_evals_per_s"],
-                            "gradient_like_for_like_env": grad_rate / cpu_line["gradient_env_evals_per_s"],
-                            "overlap": ov_rate / cpu_line["overlap_evals_per_s"],
-                            "reference_mix": ref_mix / cpu_line["reference_mix_evals_per_s"],
-                            "reference_mix_vs_node_linear_bound":
-                                ref_mix / cpu_line["node_linear_bound"]["reference_mix_evals_per_s"],
-                            "gradient_env_vs_node_linear_bound":
-                                grad_rate / cpu_line["node_linear_bound"]["gradient_env_evals_per_s"]}
-                           if cpu_line else None),
-            },
             "roofline": roof,
-            "cpu_baseline": cpu_line,
-            "parity_check": parity,
-            "latency": latency,
         }
+        if args.full:
+            by_kind["vs_cpu"] = ({"gradient": grad_rate / cpu_line["gradient_evals_per_s"],
+                                  "gradient_like_for_like_env": grad_rate / cpu_line["gradient_env_evals_per_s"],
+                                  "overlap": ov_rate / cpu_line["overlap_evals_per_s"],
+                                  "reference_mix": ref_mix / cpu_line["reference_mix_evals_per_s"],
+                                  "reference_mix_vs_node_linear_bound":
+                                      ref_mix / cpu_line["node_linear_bound"]["reference_mix_evals_per_s"],
+                                  "gradient_env_vs_node_linear_bound":
+                                      grad_rate / cpu_line["node_linear_bound"]["gradient_env_evals_per_s"]}
+                                 if cpu_line else None)
+            line.update(by_kind=by_kind, cpu_baseline=cpu_line, parity_check=parity, latency=latency)
         print(json.dumps(line))
     if world > 1:
         dist.barrier()
@@ -754,6 +787,8 @@ def strong_main(args):
     for _ in range(args.warmup):
         step()
     t_step, (best, score) = timed(step, args.steps)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, {"best_pair": best, "best_score": score})
     value = G * len(cmap) / (t_step if not sim else float("nan"))
     res = {"metric": "candidate-sweep gradient evals/sec, 50-qubit MPS chi=128 (config 4), strong scaling",
            "unit": "evals/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
