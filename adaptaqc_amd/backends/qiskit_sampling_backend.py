@@ -12,22 +12,200 @@
 # (qiskit-community/adapt-aqc) on top of the MI355X engine (libaqchip); it has been altered
 # from the original.
 
-"""Shot-sampling backend: OUT OF SCOPE.
+"""Shot-sampling backend on MI355X: drop-in for adaptaqc/backends/qiskit_sampling_backend.py:20-108.
 
-Present only so that ``python_default_backends.QASM_SIM`` exists like in the reference; any
-use raises ``NotImplementedError`` (the reference's error convention for unsupported paths).
+Costs are estimated from measurement counts, as the reference estimates them from Aer's
+``qasm_simulator``.  Here the counts come from ``SamplingSimulator``: the circuit is simulated on the
+device (statevector or MPS) and the shots are drawn there by libaqchip's samplers
+(aqc_sv_sample / aqc_mps_sample); only the outcomes come back to the host.  Any object with the
+same ``run(circuit, shots=..., **kwargs).result().get_counts()`` contract can stand in for it.
 """
+import os
+from types import SimpleNamespace
+
+import numpy as np
+
 from .aqc_backend import AQCBackend
+
+_SKIP = ("barrier", "id", "delay")
+
+
+class SamplingJob:
+    """What ``SamplingSimulator.run`` returns: the shots are drawn by the time it exists."""
+
+    def __init__(self, result):
+        self._result = result
+
+    def result(self):
+        return self._result
+
+    def status(self):
+        return "DONE"
+
+
+class SamplingResult:
+    def __init__(self, counts):
+        self._counts = counts
+
+    def get_counts(self, experiment=None):
+        return dict(self._counts)
+
+
+def _bit_index(circuit, b):
+    if isinstance(b, (int, np.integer)):
+        return int(b)
+    return int(circuit.find_bit(b).index)
+
+
+def terminal_measurements(circuit):
+    """{qubit: clbit} of the circuit's measure instructions, or None when it has none.  They must be
+    terminal: a gate after a measure on the same qubit is a mid-circuit measurement, which the
+    pure-state simulation does not run."""
+    from ..circuit import qubit_indices
+
+    measured = {}
+    for ins in circuit.data:
+        name = ins.operation.name
+        qs = qubit_indices(circuit, ins) if name != "set_matrix_product_state" else ()
+        if name == "measure":
+            measured[qs[0]] = _bit_index(circuit, ins.clbits[0])
+        elif name not in _SKIP and any(q in measured for q in qs):
+            raise NotImplementedError("a gate after a measure on the same qubit (mid-circuit measurement) is not "
+                                      "supported: measurements must be terminal")
+    return measured or None
+
+
+class SamplingSimulator:
+    """Stand-in for Aer's ``qasm_simulator`` handle held as ``backend.simulator``.
+
+    ``run(circuit, shots=1024, seed_simulator=None)`` simulates the circuit's gates on the device
+    and draws ``shots`` outcomes of its measurements there; ``result().get_counts()`` gives qiskit's
+    counts dict (bitstrings over the classical bits, highest leftmost; over all qubits for a circuit
+    without measure instructions).  ``method``: "statevector", "matrix_product_state", or
+    "automatic" (statevector up to 26 qubits, MPS above).
+
+    The simulated state is kept, keyed by the gate list (measures are not part of the key), so the
+    reference's local cost -- n runs that differ only in the measured qubit
+    (qiskit_sampling_backend.py:46-76) -- simulates once and samples n times.
+
+    With ``seed_simulator`` the shots depend on that seed alone (identical calls give identical
+    counts, as with Aer); without it the seed is drawn at construction (or is ``seed``) and every
+    run advances a run counter, so repeated runs are independent."""
+
+    name = "hip_sampling_simulator"
+    METHODS = ("automatic", "statevector", "matrix_product_state")
+
+    def __init__(self, method="automatic", seed=None, mps_truncation_threshold=1e-16, max_chi=None):
+        if method not in self.METHODS:
+            raise ValueError(f"method must be one of {self.METHODS}")
+        self.options = SimpleNamespace(method=method, matrix_product_state_truncation_threshold=mps_truncation_threshold,
+                                       matrix_product_state_max_bond_dimension=max_chi)
+        self.seed = int(seed) if seed is not None else int(np.random.SeedSequence().generate_state(2, np.uint32).view(np.uint64)[0])
+        self.runs = 0
+        self._last = None  # (n, method, ops bytes, device state)
+
+    def __getstate__(self):
+        d = dict(self.__dict__)
+        d["_last"] = None
+        d.pop("aqc_learned_cap", None)
+        return d
+
+    def __repr__(self):
+        return f"SamplingSimulator(hip, gfx950, method={self.options.method!r})"
+
+    def _method(self, n):
+        m = self.options.method
+        if m == "automatic":
+            return "statevector" if n <= 26 else "matrix_product_state"
+        return m
+
+    def _state(self, circuit):
+        from ..circuit import device_ops_array
+        from ..device import DeviceSV
+        from ..mps_operations import device_mps_from_circuit
+
+        n = circuit.num_qubits
+        method = self._method(n)
+        key = device_ops_array(circuit).tobytes()
+        if self._last is not None and self._last[:3] == (n, method, key):
+            return self._last[3]
+        if method == "statevector":
+            dev = DeviceSV(n)
+            dev.apply(device_ops_array(circuit))
+        else:
+            dev = device_mps_from_circuit(circuit, sim=self)
+        self._last = (n, method, key, dev)
+        return dev
+
+    def run(self, circuit, shots=1024, seed_simulator=None, **ignored):
+        from ..device import counts_from_samples
+
+        measured = terminal_measurements(circuit)
+        dev = self._state(circuit)
+        if seed_simulator is not None:
+            seed, run = int(seed_simulator), 0
+        else:
+            seed, run = self.seed, self.runs
+            self.runs += 1
+        samples = dev.sample(int(shots), seed, run)
+        counts = counts_from_samples(samples, circuit.num_qubits, measured)
+        if measured is not None:  # keys over every classical bit: an unmeasured one reads 0
+            width = max(int(getattr(circuit, "num_clbits", 0) or 0), max(measured.values()) + 1)
+            counts = {k.rjust(width, "0"): v for k, v in counts.items()}
+        return SamplingJob(SamplingResult(counts))
 
 
 class QiskitSamplingBackend(AQCBackend):
     def __init__(self, simulator=None):
-        self.simulator = simulator
+        self.simulator = simulator if simulator is not None else SamplingSimulator()
 
-    def _unsupported(self, *_):
-        raise NotImplementedError("shot-sampling (qasm_simulator) backend is not part of the MI355X hot path")
+    def evaluate_global_cost(self, compiler):
+        """qiskit_sampling_backend.py:24-44: 1 - (share of shots that read all zeros)."""
+        if compiler.soften_global_cost:
+            raise NotImplementedError("soften_global_cost is currently only implemented for AerMPSBackend")
+        counts = self.evaluate_circuit(compiler)
+        width = compiler.total_num_qubits * (2 if compiler.general_initial_state else 1)
+        return 1 - _share(counts, "0" * width)
 
-    evaluate_global_cost = _unsupported
-    evaluate_local_cost = _unsupported
-    evaluate_circuit = _unsupported
-    measure_qubit_expectation_values = _unsupported
+    def evaluate_local_cost(self, compiler):
+        """qiskit_sampling_backend.py:46-76: per qubit (with its partner under general_initial_state),
+        measure, run, remove the measure; the cost is the mean share of shots not reading zero."""
+        n = compiler.total_num_qubits
+        circuit = compiler.full_circuit
+        qubit_costs = np.zeros(n)
+        for i in range(n):
+            qubits = (i, i + n) if compiler.general_initial_state else (i,)
+            for clbit, q in enumerate(qubits):
+                circuit.measure(q, clbit)
+            try:
+                counts = self.evaluate_circuit(compiler)
+            finally:
+                del circuit.data[-len(qubits):]
+            qubit_costs[i] = 1 - _share(counts, "0" * len(qubits))
+        return np.mean(qubit_costs)
+
+    def evaluate_circuit(self, compiler):
+        # Don't parallelise shots if ADAPT-AQC is already being run in parallel (reference :79-81);
+        # backend_options (method / max_parallel_experiments) are Aer's and have no meaning here.
+        _ = os.environ["QISKIT_IN_PARALLEL"] == "TRUE"
+        job = self.simulator.run(compiler.full_circuit, **compiler.execute_kwargs)
+        return job.result().get_counts()
+
+    def measure_qubit_expectation_values(self, compiler):
+        """qiskit_sampling_backend.py:91-108: <Z_i> = (shots reading 0 - shots reading 1) / shots of
+        bit i (bit 0 is the rightmost character)."""
+        counts = self.evaluate_circuit(compiler)
+        keys = list(counts)
+        width = len(keys[0])
+        total = sum(counts.values())
+        out = []
+        for i in range(width):
+            pos = width - 1 - i
+            out.append(sum((1 if k[pos] == "0" else -1) * counts[k] for k in keys) / total)
+        return out
+
+
+def _share(counts, key):
+    """counts[key] / shots; a key no shot produced is absent from the dict (share 0)."""
+    total = sum(counts.values())
+    return counts.get(key, 0) / total

@@ -103,6 +103,7 @@ class CircuitInstruction:
 class QuantumCircuit:
     def __init__(self, num_qubits: int):
         self.num_qubits = int(num_qubits)
+        self.num_clbits = 0  # grows with measure()
         self.data: list[CircuitInstruction] = []
 
     # -- construction ------------------------------------------------------------------
@@ -206,6 +207,18 @@ class QuantumCircuit:
     def barrier(self, *args):
         return self
 
+    def measure(self, qubit, clbit):
+        """Measure ``qubit`` into classical bit ``clbit`` (the shot-sampling backend reads these;
+        the op conversion skips them).  The classical register grows as needed."""
+        qubit, clbit = int(qubit), int(clbit)
+        if not 0 <= qubit < self.num_qubits:
+            raise IndexError(f"qubit {qubit} out of range for {self.num_qubits}-qubit circuit")
+        if clbit < 0:
+            raise IndexError("classical bit index must not be negative")
+        self.num_clbits = max(self.num_clbits, clbit + 1)
+        self.data.append(CircuitInstruction(Operation("measure", 1), [qubit], (clbit,)))
+        return self
+
     def find_bit(self, q):
         """qiskit's ``find_bit``: here qubits are their own indices."""
         return BitLocation(int(q))
@@ -235,6 +248,7 @@ class QuantumCircuit:
 
     def copy(self):
         qc = QuantumCircuit(self.num_qubits)
+        qc.num_clbits = self.num_clbits
         qc.data = [i.copy() for i in self.data]
         return qc
 
@@ -546,9 +560,14 @@ def qasm2_dumps(circuit) -> str:
     """OpenQASM 2.0 text of a circuit (``qiskit.qasm2.dumps``; adapt_compiler.py:359-366 keeps
     one per layer in ``circuit_history``).  Gates outside qelib1 are unrolled (_qasm_pieces)."""
     lines = ["OPENQASM 2.0;", 'include "qelib1.inc";', f"qreg q[{circuit.num_qubits}];"]
+    if getattr(circuit, "num_clbits", 0):
+        lines.append(f"creg c[{circuit.num_clbits}];")
     for ins in circuit.data:
         op = ins.operation
         if op.name in ("barrier", "delay"):
+            continue
+        if op.name == "measure":
+            lines.append(f"measure q[{qubit_indices(circuit, ins)[0]}] -> c[{int(ins.clbits[0])}];")
             continue
         for name, params, qs in _qasm_pieces(op, qubit_indices(circuit, ins)):
             ps = "(" + ",".join(repr(float(p)) for p in params) + ")" if params else ""

@@ -89,6 +89,11 @@ class AdaptCompiler(ApproximateCompiler):
         self.layers_as_gates = []
         self.resume_from_layer = None
         self.prev_checkpoint_time_taken = None
+        if self.adapt_config.method == "ISL" and self.is_sampling_backend:
+            # (the reference measures pair entanglement there by state tomography of the counts,
+            # entanglement_measures.py:100-180, which this build does not restate)
+            raise NotImplementedError("method 'ISL' needs a statevector or MPS backend: with the shot-sampling "
+                                      "backend use 'expectation', 'random', 'basic' or 'brickwall'")
         if self.adapt_config.method == "general_gradient":
             if not self.is_aer_mps_backend:
                 raise ValueError("general_gradient method is only implemented for Aer MPS backend")

@@ -23,6 +23,7 @@ from abc import ABC, abstractmethod
 
 from ..backends.aer_mps_backend import AerMPSBackend
 from ..backends.python_default_backends import SV_SIM
+from ..backends.qiskit_sampling_backend import QiskitSamplingBackend
 from ..circuit import QuantumCircuit
 from ..mps_operations import check_mps, mps_from_circuit, zero_aer_mps, _preprocess_mps
 from ..utils import circuit_operations as co
@@ -87,8 +88,10 @@ class ApproximateCompiler(ABC):
         if check_mps(self.target) and not self.is_aer_mps_backend:
             raise Exception("Aer MPS backend must be used when target is an Aer MPS")
         self.circuit_to_compile = self.prepare_circuit()
+        self.is_sampling_backend = isinstance(self.backend, QiskitSamplingBackend)
         self.execute_kwargs = dict(execute_kwargs or {})
-        self.execute_kwargs.setdefault("shots", 1)
+        # approximate_compiler.py:248-257
+        self.execute_kwargs.setdefault("shots", 8192 if self.is_sampling_backend else 1)
         self.execute_kwargs.setdefault("optimization_level", 0)
         self.backend_options = {"method": "automatic"}
         if (initial_state is not None or general_initial_state) and self.is_aer_mps_backend:
@@ -189,6 +192,11 @@ class ApproximateCompiler(ABC):
             for q in range(n - 1, -1, -1):
                 qc.cx(q, q + n)
                 qc.h(q)
+        if self.is_sampling_backend and not self.optimise_local_cost:
+            # approximate_compiler.py:502-508: the global cost reads every qubit (the local cost adds
+            # and removes its own measures per evaluation); the measures count in rhs_gate_count
+            for q in range(qc.num_qubits):
+                qc.measure(q, q)
         return qc, lhs, len(qc.data) - lhs
 
     def get_compiled_circuit(self):

@@ -194,6 +194,9 @@ int upload_async(void* dst, const void* pinned_src, size_t bytes, hipStream_t st
 void* dev_alloc(size_t bytes);
 void dev_free(void* p);
 
+// The statevector handle as the samplers (sample.hip) read it (sv.hip).
+int sv_view(aqc_sv_t h, const cplx** state, int* n, hipStream_t* stream);
+
 // ---- kernel timing (HIP events on the launching stream) ------------------------------
 struct KernelTimer {
   // Begin/End bracket one launch on `stream` when timing is enabled.

@@ -1083,6 +1083,55 @@ int launch_zenv(const ZJob* dj, int nch, int cap, hipStream_t st, unsigned* cnt,
 
 }  // namespace
 
+// The environment chains of aqc_mps_z_all_batch for one state, left in the per-device buffer for a
+// caller in another translation unit (the MPS sampler): see mps_internal.h.
+int aqc::mps_right_envs(aqc_mps_s* h, size_t extra_bytes, const cplx** renv, void** extra, hipStream_t* stream) {
+  const int n = h->d.n, cap = h->d.cap;
+  const size_t cc = (size_t)cap * cap;
+  const size_t per_state = (2 * (size_t)(n + 1) * cc + 4 * cc) * sizeof(cplx);
+  const size_t jb = ((sizeof(RdmJob) + 255) / 256) * 256;
+  hipStream_t st = aqc::mps_stream();
+  RdmBuffers& rb = rbuf();
+  AQC_HIP_CHECK(hipStreamSynchronize(st));
+  const size_t sb = env_sync_bytes(1);
+  int rc = ensure(rb, jb + per_state + sb + extra_bytes + 1024);
+  if (rc != AQC_OK) return rc;
+  char* base = (char*)rb.dev;
+  RdmJob* djobs = (RdmJob*)base;
+  cplx* work = (cplx*)(base + jb);
+  void* dsync = base + jb + per_state;
+  RdmJob j;
+  std::memset(&j, 0, sizeof(j));
+  j.gam = h->d.gam;
+  j.lam = h->d.lam;
+  j.dims = h->d.dims;
+  j.n = n;
+  j.cap = cap;
+  j.Lenv = work;
+  j.Renv = work + (size_t)(n + 1) * cc;
+  j.tmpL = j.Renv + (size_t)(n + 1) * cc;
+  j.tmpR = j.tmpL + 2 * cc;
+  AQC_HIP_CHECK(hipMemcpyAsync(djobs, &j, sizeof(RdmJob), hipMemcpyHostToDevice, st));
+  const double c3 = (double)cap * cap * cap;
+  for (int attempt = 0;; ++attempt) {  // attempt 1: the split chains timed out, single-workgroup chains
+    aqc::KernelTimer::begin(st, "sample_env", 0.0, 2.0 * n * 4.0 * c3 * 8.0);
+    rc = launch_envs(djobs, 1, cap, st, dsync, attempt > 0);
+    aqc::KernelTimer::end(st);
+    if (rc != AQC_OK) return rc;
+    AQC_HIP_CHECK(hipStreamSynchronize(st));
+    bool again = false;
+    if (attempt == 0) {
+      rc = env_timed_out(dsync, 1, cap, again);
+      if (rc != AQC_OK) return rc;
+    }
+    if (!again) break;
+  }
+  *renv = j.Renv;
+  *extra = base + jb + per_state + sb;
+  *stream = st;
+  return AQC_OK;
+}
+
 extern "C" {
 
 int aqc_mps_pair_rdms_batch(aqc_mps_t* hs, int ns, const int* pairs, int npairs, double* out, int out_is_device) {

@@ -245,6 +245,15 @@ hipStream_t mps_stream_if_any(int dev);
 
 }  // namespace aqc
 
+// The right environments R_1 .. R_n of one state in sorted qubit order (ent.hip: the chains that
+// aqc_mps_z_all_batch runs at the state's capacity, with its single-workgroup re-run after a
+// hand-off timeout), complete when the call returns: R_b at renv + b cap^2, row-major with row
+// stride cap.  They live in ent.hip's per-device buffer until its next use, followed by `extra_bytes`
+// of workspace for the caller (256-byte aligned); *stream is the library's stream.
+namespace aqc {
+int mps_right_envs(aqc_mps_s* h, size_t extra_bytes, const cplx** renv, void** extra, hipStream_t* stream);
+}
+
 struct aqc_mps_s {
   aqc::MpsDev d;
   double thr = 1e-16;

@@ -911,6 +911,16 @@ static int sv_materialize(aqc_sv_t h) {
   return AQC_OK;
 }
 
+// The state as the samplers (sample.hip) read it: the amplitudes (a deferred reset materialised), the
+// qubit count and the handle's stream.
+int aqc::sv_view(aqc_sv_t h, const cplx** state, int* n, hipStream_t* stream) {
+  if (int rc = sv_materialize(h)) return rc;
+  *state = h->state;
+  *n = h->n;
+  *stream = h->stream;
+  return AQC_OK;
+}
+
 static int sv_scratch(aqc_sv_t h, size_t bytes, char** out) {
   if (bytes > h->scratch_cap) {
     AQC_HIP_CHECK(hipStreamSynchronize(h->stream));

@@ -59,6 +59,15 @@ class DeviceSV:
             _lib.check(self._l.aqc_sv_pair_rdms(self.h, _lib.ptr(pairs), len(pairs) // 2, _lib.ptr(out)))
         return out.reshape(-1, 4, 4)
 
+    def sample(self, shots, seed, run=0, u=None):
+        """``shots`` measurement outcomes of all qubits (aqc_sv_sample): uint64[shots] basis
+        indices (bit q = qubit q).  ``u``: shots uniforms in [0, 1) used instead of the generator's."""
+        shots = int(shots)
+        out = np.zeros(max(shots, 0), dtype=np.uint64)
+        up = _uniforms_arg(u, (shots,))
+        _lib.check(self._l.aqc_sv_sample(self.h, shots, _u64(seed), _u64(run), _lib.ptr(up), _lib.ptr(out)))
+        return out
+
     def get(self):
         out = np.zeros(2 ** self.n, dtype=np.complex128)
         _lib.check(self._l.aqc_sv_get(self.h, _lib.ptr(out)))
@@ -185,6 +194,16 @@ class DeviceMPS:
         _lib.check(self._l.aqc_mps_amps_hw1(self.h, _lib.ptr(out)))
         return out[0::2] + 1j * out[1::2]
 
+    def sample(self, shots, seed, run=0, u=None):
+        """``shots`` measurement outcomes of all qubits (aqc_mps_sample): uint64[shots, words],
+        bit q % 64 of word q // 64 = outcome of qubit q.  ``u``: [shots, n] uniforms in [0, 1) used
+        instead of the generator's."""
+        shots = int(shots)
+        out = np.zeros((max(shots, 0), (self.n + 63) // 64), dtype=np.uint64)
+        up = _uniforms_arg(u, (shots, self.n))
+        _lib.check(self._l.aqc_mps_sample(self.h, shots, _u64(seed), _u64(run), _lib.ptr(up), _lib.ptr(out)))
+        return out
+
     def product_fit(self, svec=None, min_sweeps=10, max_sweeps=50, tol=1e-12):
         """Best product-state approximation (aqc_mps_product_fit): returns (svec (n, 2), fidelity,
         sweeps).  svec None starts from the chi = 1 truncation of the canonical form."""
@@ -204,6 +223,63 @@ class DeviceMPS:
         if len(pairs):
             _lib.check(self._l.aqc_mps_pair_rdms(self.h, _lib.ptr(pairs), len(pairs) // 2, _lib.ptr(out)))
         return out.reshape(-1, 4, 4)
+
+
+def _u64(x):
+    return ctypes.c_uint64(int(x) & 0xFFFFFFFFFFFFFFFF)
+
+
+def _uniforms_arg(u, shape):
+    if u is None:
+        return None
+    u = np.ascontiguousarray(u, dtype=np.float64)
+    if u.shape != tuple(shape):
+        raise ValueError(f"sample: u must have shape {tuple(shape)}")
+    return u
+
+
+def sample_uniforms(seed, run, shots, nper):
+    """The uniforms the samplers draw for (seed, run): [shots, nper] (aqc_sample_uniforms)."""
+    out = np.zeros((int(shots), int(nper)))
+    _lib.check(_lib.lib().aqc_sample_uniforms(_u64(seed), _u64(run), int(shots), int(nper), _lib.ptr(out)))
+    return out
+
+
+def counts_from_samples(samples, n, clbit_of_qubit=None):
+    """Counts dict of qiskit bitstrings (highest bit leftmost) from sampler output: uint64[shots]
+    basis indices (n <= 64) or uint64[shots, words] packed words.  ``clbit_of_qubit``: {qubit:
+    clbit}; the keys then run over the clbits max(clbit) .. 0, an unwritten clbit reading 0;
+    None: the keys run over all n qubits."""
+    s = np.asarray(samples, dtype=np.uint64)
+    if s.ndim == 1:
+        s = s.reshape(-1, 1)
+    if s.shape[1] * 64 < n:
+        raise ValueError("counts_from_samples: too few words for n qubits")
+    if clbit_of_qubit is None:
+        width = int(n)
+        cols = s[:, : (width + 63) // 64]
+        if width % 64:
+            cols = cols.copy()
+            cols[:, -1] &= np.uint64((1 << (width % 64)) - 1)
+    else:
+        width = max(clbit_of_qubit.values()) + 1 if clbit_of_qubit else 0
+        cols = np.zeros((s.shape[0], max(1, (width + 63) // 64)), dtype=np.uint64)
+        for q, c in clbit_of_qubit.items():
+            if not 0 <= q < n:
+                raise ValueError("counts_from_samples: measured qubit out of range")
+            bit = (s[:, q // 64] >> np.uint64(q % 64)) & np.uint64(1)
+            mask = ~(np.uint64(1) << np.uint64(c % 64))
+            cols[:, c // 64] = (cols[:, c // 64] & mask) | (bit << np.uint64(c % 64))  # (a later measure overwrites)
+    if s.shape[0] == 0:
+        return {}
+    vals, cnt = np.unique(np.ascontiguousarray(cols), axis=0, return_counts=True)
+    out = {}
+    for v, c in zip(vals, cnt):
+        x = 0
+        for w in range(len(v) - 1, -1, -1):
+            x = (x << 64) | int(v[w])
+        out[format(x, f"0{max(width, 1)}b")[-max(width, 1):]] = int(c)
+    return out
 
 
 def _handles(states):

@@ -136,6 +136,24 @@ int aqc_sv_transition(aqc_sv_t bra, aqc_sv_t ket, int q, double* out);
    3 = log-negativity.  rdms / out in device memory when on_device. */
 int aqc_entanglement_measures(const double* rdms, int count, int method, double* out, int on_device);
 
+/* ---- shot sampling: replaces the counts of qiskit_sampling_backend.py:78-89 (Aer qasm_simulator) ----
+   Random numbers are counter based, Philox4x32-10 with key = (seed & 0xffffffff, seed >> 32) and
+   counter = (shot & 0xffffffff, shot >> 32, site, run & 0xffffffff); the uniform of a counter is
+   u = ((x0 >> 5) * 2^26 + (x1 >> 6)) * 2^-53 from output words x0, x1.  A shot's outcome depends only
+   on (seed, run, shot, site).  Neither sampler modifies the state.
+   nshots outcomes of measuring every qubit of the state; out[j] = basis index (bit q = qubit q):
+   the smallest k whose inclusive prefix sum of |psi_k|^2 exceeds u * total (site = 0).
+   u == NULL: uniforms from (seed, run) as above; else nshots host doubles in [0,1) used instead.
+   nshots < 1 (or above 2^30) or a u outside [0,1): AQC_ERR_ARG. */
+int aqc_sv_sample(aqc_sv_t h, int nshots, uint64_t seed, uint64_t run, const double* u, uint64_t* out);
+/* As above for an MPS (sorted to qubit order first, like every measurement): out is
+   nshots x ((n+63)/64) words, bit q%64 of word q/64 = outcome of qubit q; u: NULL or nshots x n,
+   [shot][site].  Site by site against the right environments (no canonical form assumed): with
+   w_s = v A_i^s and p_s = Re(w_s R_{i+1} w_s^dag), bit = 1 iff u (p_0 + p_1) >= p_0, then
+   v = w_bit / sqrt(p_bit).  A pending capacity or SVD flag of queued work: AQC_ERR_STATE, as in
+   aqc_mps_overlap_zero. */
+int aqc_mps_sample(aqc_mps_t h, int nshots, uint64_t seed, uint64_t run, const double* u, uint64_t* out);
+
 /* move_all_qubits_to_sorted_ordering (done implicitly by every measurement below). */
 int aqc_mps_sort(aqc_mps_t h);
 int aqc_mps_sort_batch(aqc_mps_t* hs, int nstates);

@@ -121,6 +121,10 @@ int aqc_svd_debug(const double* theta, int m, int n, int variant, int stop_after
  * matrices over ~sqrt(n) segments as batched MFMA GEMMs) for every single state.  Results are the
  * same up to floating-point summation order. */
 int aqc_sweep_set_chain_mode(int mode);
+/* The uniforms the samplers (aqc_sv_sample / aqc_mps_sample with u == NULL) draw for (seed, run):
+   out[shot * nper + site], generated on the device and copied to the host (tests pin the generator
+   with it). */
+int aqc_sample_uniforms(uint64_t seed, uint64_t run, int nshots, int nper, double* out);
 #ifdef __cplusplus
 }
 #endif
