@@ -41,6 +41,7 @@ EXPORTS = (
     "aqc_gb_set_spin_limit", "aqc_gb_set_tail", "aqc_gb_set_stages", "aqc_debug_hog", "aqc_pool_stats",
     "aqc_env_fallbacks", "aqc_env_set_single", "aqc_env_set_spin_limit",
     "aqc_sv_sample", "aqc_mps_sample", "aqc_sample_uniforms",
+    "aqc_sv_pauli_expect", "aqc_mps_pauli_expect", "aqc_mps_pauli_expect_batch",
 )
 
 
@@ -145,6 +146,9 @@ _SIGS = {
     "aqc_sv_sample": ([_P, _I, ctypes.c_uint64, ctypes.c_uint64, _P, _P], _I),
     "aqc_mps_sample": ([_P, _I, ctypes.c_uint64, ctypes.c_uint64, _P, _P], _I),
     "aqc_sample_uniforms": ([ctypes.c_uint64, ctypes.c_uint64, _I, _I, _P], _I),
+    "aqc_sv_pauli_expect": ([_P, _P, _P, _I, _P], _I),
+    "aqc_mps_pauli_expect": ([_P, _P, _I, _P], _I),
+    "aqc_mps_pauli_expect_batch": ([_P, _I, _P, _I, _P], _I),
 }
 
 

@@ -1132,6 +1132,60 @@ int aqc::mps_right_envs(aqc_mps_s* h, size_t extra_bytes, const cplx** renv, voi
   return AQC_OK;
 }
 
+// The same chains for a batch of states of one n and capacity, handing out both sides (the Pauli
+// chains of pauli.hip): see mps_internal.h.
+int aqc::mps_envs_batch(aqc_mps_s** hs, int ns, size_t extra_bytes, const char* family, const cplx** lenv,
+                        size_t* state_stride, void** extra, hipStream_t* stream) {
+  const int n = hs[0]->d.n, cap = hs[0]->d.cap;
+  const size_t cc = (size_t)cap * cap;
+  const size_t per_state = (2 * (size_t)(n + 1) * cc + 4 * cc) * sizeof(cplx);
+  const size_t jb = (((size_t)ns * sizeof(RdmJob) + 255) / 256) * 256;
+  hipStream_t st = aqc::mps_stream();
+  RdmBuffers& rb = rbuf();
+  AQC_HIP_CHECK(hipStreamSynchronize(st));
+  const size_t sb = env_sync_bytes(ns);
+  int rc = ensure(rb, jb + (size_t)ns * per_state + sb + extra_bytes + 1024);
+  if (rc != AQC_OK) return rc;
+  char* base = (char*)rb.dev;
+  RdmJob* djobs = (RdmJob*)base;
+  cplx* work = (cplx*)(base + jb);
+  void* dsync = base + jb + (size_t)ns * per_state;
+  std::vector<RdmJob> jobs(ns);
+  for (int s = 0; s < ns; ++s) {
+    RdmJob& j = jobs[s];
+    std::memset(&j, 0, sizeof(j));
+    j.gam = hs[s]->d.gam;
+    j.lam = hs[s]->d.lam;
+    j.dims = hs[s]->d.dims;
+    j.n = n;
+    j.cap = cap;
+    j.Lenv = work + (size_t)s * (per_state / sizeof(cplx));
+    j.Renv = j.Lenv + (size_t)(n + 1) * cc;
+    j.tmpL = j.Renv + (size_t)(n + 1) * cc;
+    j.tmpR = j.tmpL + 2 * cc;
+  }
+  AQC_HIP_CHECK(hipMemcpyAsync(djobs, jobs.data(), (size_t)ns * sizeof(RdmJob), hipMemcpyHostToDevice, st));
+  const double c3 = (double)cap * cap * cap;
+  for (int attempt = 0;; ++attempt) {  // attempt 1: the split chains timed out, single-workgroup chains
+    aqc::KernelTimer::begin(st, family, 0.0, ns * 2.0 * n * 4.0 * c3 * 8.0);
+    rc = launch_envs(djobs, ns, cap, st, dsync, attempt > 0);
+    aqc::KernelTimer::end(st);
+    if (rc != AQC_OK) return rc;
+    AQC_HIP_CHECK(hipStreamSynchronize(st));
+    bool again = false;
+    if (attempt == 0) {
+      rc = env_timed_out(dsync, ns, cap, again);
+      if (rc != AQC_OK) return rc;
+    }
+    if (!again) break;
+  }
+  *lenv = work;
+  *state_stride = per_state / sizeof(cplx);
+  *extra = base + jb + (size_t)ns * per_state + sb;
+  *stream = st;
+  return AQC_OK;
+}
+
 extern "C" {
 
 int aqc_mps_pair_rdms_batch(aqc_mps_t* hs, int ns, const int* pairs, int npairs, double* out, int out_is_device) {

@@ -252,6 +252,12 @@ hipStream_t mps_stream_if_any(int dev);
 // of workspace for the caller (256-byte aligned); *stream is the library's stream.
 namespace aqc {
 int mps_right_envs(aqc_mps_s* h, size_t extra_bytes, const cplx** renv, void** extra, hipStream_t* stream);
+// Both sides for ns states of one n and capacity (sorted; the caller checks that), from the same
+// chains in one set of launches: state s has L_0 .. L_{n-1} ([bra][ket]) at lenv + s state_stride +
+// b cap^2 and R_1 .. R_n ([ket][bra]) (n + 1) cap^2 elements further, row stride cap.  `family`
+// names the launches for aqc_timing_query; the rest as above (*extra is 16-byte aligned).
+int mps_envs_batch(aqc_mps_s** hs, int ns, size_t extra_bytes, const char* family, const cplx** lenv,
+                   size_t* state_stride, void** extra, hipStream_t* stream);
 }
 
 struct aqc_mps_s {

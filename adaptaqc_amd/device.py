@@ -68,6 +68,25 @@ class DeviceSV:
         _lib.check(self._l.aqc_sv_sample(self.h, shots, _u64(seed), _u64(run), _lib.ptr(up), _lib.ptr(out)))
         return out
 
+    def pauli_expect(self, terms):
+        """Re <psi|P_t|psi> of every Pauli string in one launch (aqc_sv_pauli_expect).  ``terms``: a
+        list of qiskit labels (rightmost character = qubit 0) or an (nterms, n) uint8 code array
+        (0 I, 1 X, 2 Y, 3 Z; column q = qubit q)."""
+        from . import paulis
+
+        x, z = paulis.codes_to_masks(paulis.terms_to_codes(terms, self.n))
+        return self.pauli_expect_masks(x, z)
+
+    def pauli_expect_masks(self, xmask, zmask):
+        """The same from bit masks (bit q = qubit q; a qubit in both masks is Y)."""
+        x = np.ascontiguousarray(xmask, dtype=np.uint64).reshape(-1)
+        z = np.ascontiguousarray(zmask, dtype=np.uint64).reshape(-1)
+        if len(x) != len(z):
+            raise ValueError("pauli_expect_masks: one x and one z mask per term")
+        out = np.zeros(len(x))
+        _lib.check(self._l.aqc_sv_pauli_expect(self.h, _lib.ptr(x), _lib.ptr(z), len(x), _lib.ptr(out)))
+        return out
+
     def get(self):
         out = np.zeros(2 ** self.n, dtype=np.complex128)
         _lib.check(self._l.aqc_sv_get(self.h, _lib.ptr(out)))
@@ -202,6 +221,17 @@ class DeviceMPS:
         out = np.zeros((max(shots, 0), (self.n + 63) // 64), dtype=np.uint64)
         up = _uniforms_arg(u, (shots, self.n))
         _lib.check(self._l.aqc_mps_sample(self.h, shots, _u64(seed), _u64(run), _lib.ptr(up), _lib.ptr(out)))
+        return out
+
+    def pauli_expect(self, terms):
+        """<psi|P_t|psi> of every Pauli string (aqc_mps_pauli_expect), not divided by <psi|psi> (the
+        convention of z_all).  ``terms``: qiskit labels (rightmost character = qubit 0) or an
+        (nterms, n) uint8 code array (0 I, 1 X, 2 Y, 3 Z; column q = qubit q)."""
+        from . import paulis
+
+        codes = paulis.terms_to_codes(terms, self.n)
+        out = np.zeros(len(codes))
+        _lib.check(self._l.aqc_mps_pauli_expect(self.h, _lib.ptr(codes), len(codes), _lib.ptr(out)))
         return out
 
     def product_fit(self, svec=None, min_sweeps=10, max_sweeps=50, tol=1e-12):
@@ -366,6 +396,21 @@ def z_all_batch(states):
     out = np.zeros(len(states) * n)
     _lib.check(_lib.lib().aqc_mps_z_all_batch(_handles(states), len(states), _lib.ptr(out)))
     return out.reshape(len(states), n)
+
+
+def pauli_expect_batch(states, terms):
+    """<psi_s|P_t|psi_s> as rows per state, one set of launches for every (term, state)
+    (aqc_mps_pauli_expect_batch); the states need the same n and capacity.  ``terms`` as
+    DeviceMPS.pauli_expect."""
+    from . import paulis
+
+    if not states:
+        return np.zeros((0, 0))
+    codes = paulis.terms_to_codes(terms, states[0].n)
+    out = np.zeros(len(states) * len(codes))
+    _lib.check(_lib.lib().aqc_mps_pauli_expect_batch(_handles(states), len(states), _lib.ptr(codes), len(codes),
+                                                     _lib.ptr(out)))
+    return out.reshape(len(states), len(codes))
 
 
 def z_sum_batch(base, states):

@@ -232,9 +232,18 @@ def mps_dot(a, b, already_preprocessed=False):
 
 
 def mps_expectation(mps, operator, qubit, already_preprocessed=False):
-    if operator != "Z":
-        raise NotImplementedError("only Z expectations are on the hot path")
-    return float(_as_device(mps, already_preprocessed).z_all()[qubit])
+    d = _as_device(mps, already_preprocessed)
+    if operator == "Z":
+        return float(d.z_all()[qubit])
+    if operator not in ("I", "X", "Y"):
+        raise ValueError(f"mps_expectation: operator must be one of I, X, Y, Z, got {operator!r}")
+    if not 0 <= int(qubit) < d.n:
+        raise ValueError(f"mps_expectation: qubit {qubit} out of range for {d.n} qubits")
+    from .paulis import CODES
+
+    codes = np.zeros((1, d.n), dtype=np.uint8)
+    codes[0, int(qubit)] = CODES[operator]
+    return float(d.pauli_expect(codes)[0])
 
 
 def extract_amplitude(mps, index, already_preprocessed=False):

@@ -49,6 +49,17 @@ def is_statevector_backend(backend):
     return isinstance(backend, AerSVBackend)
 
 
+def expectation_value_of_pauli_observable(counts, pauli_label):
+    """utilityfunctions.py:236-259: the parity average of the counts over the qubits where the label
+    is not I (the label and the keys are read right to left: character -1 - q is qubit q).  The
+    reference takes a qiskit ``Pauli``; here the label itself."""
+    from ..paulis import label_to_codes, parity_from_counts
+
+    label = pauli_label if isinstance(pauli_label, str) else pauli_label.to_label()
+    codes = label_to_codes(label)
+    return parity_from_counts(counts, [q for q, c in enumerate(codes) if c])
+
+
 def remove_permutations_from_coupling_map(coupling_map):
     seen, unique = set(), []
     for pair in coupling_map:

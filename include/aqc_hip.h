@@ -154,6 +154,25 @@ int aqc_sv_sample(aqc_sv_t h, int nshots, uint64_t seed, uint64_t run, const dou
    aqc_mps_overlap_zero. */
 int aqc_mps_sample(aqc_mps_t h, int nshots, uint64_t seed, uint64_t run, const double* u, uint64_t* out);
 
+/* ---- Pauli-string expectation values: replaces circuit_operations_pauli_ops.py:60-100 -------------
+   (expectation_value_of_pauli_operator, which runs one rotated circuit per term).
+   out[t] = Re <psi| P_t |psi>,  P_t = i^{popcount(x&z)} X^{x} Z^{z}  (a qubit set in both masks is Y);
+   bit q of a mask = qubit q.  A mask bit at or above n: AQC_ERR_ARG.  Does not modify the state.
+   All terms go in one launch; sums run in a fixed order (no atomics): the same state gives the
+   same bits. */
+int aqc_sv_pauli_expect(aqc_sv_t h, const uint64_t* xmask, const uint64_t* zmask, int nterms, double* out);
+/* codes: nterms x n bytes, codes[t*n + q] in {0 I, 1 X, 2 Y, 3 Z} for qubit q; out: nterms doubles
+   (batch: nstates x nterms).  The states are sorted to qubit order first, as every measurement.
+   <psi|P|psi> is NOT divided by <psi|psi>: same convention as aqc_mps_z_all, so a truncated state
+   gives the same number z_all gives for a single Z, and the all-identity term gives <psi|psi>.
+   Pending capacity / SVD flags of queued work: AQC_ERR_STATE, as aqc_mps_overlap_zero.
+   Batch: all states need the same n and capacity (AQC_ERR_ARG otherwise).  A code above 3: AQC_ERR_ARG.
+   The identity environments of every bond come from the chains of aqc_mps_z_all_batch; each
+   (term, state) then runs its support's transfer steps in one workgroup of its own (no
+   synchronisation between workgroups), so at capacity 1024 a long string is slow but correct. */
+int aqc_mps_pauli_expect(aqc_mps_t h, const uint8_t* codes, int nterms, double* out);
+int aqc_mps_pauli_expect_batch(aqc_mps_t* hs, int nstates, const uint8_t* codes, int nterms, double* out);
+
 /* move_all_qubits_to_sorted_ordering (done implicitly by every measurement below). */
 int aqc_mps_sort(aqc_mps_t h);
 int aqc_mps_sort_batch(aqc_mps_t* hs, int nstates);
