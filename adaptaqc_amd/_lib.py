@@ -42,6 +42,7 @@ EXPORTS = (
     "aqc_env_fallbacks", "aqc_env_set_single", "aqc_env_set_spin_limit",
     "aqc_sv_sample", "aqc_mps_sample", "aqc_sample_uniforms",
     "aqc_sv_pauli_expect", "aqc_mps_pauli_expect", "aqc_mps_pauli_expect_batch",
+    "aqc_pair_tomo_probs", "aqc_concurrence_bound_probs", "aqc_multinomial_counts", "aqc_tomo_fit",
 )
 
 
@@ -149,6 +150,10 @@ _SIGS = {
     "aqc_sv_pauli_expect": ([_P, _P, _P, _I, _P], _I),
     "aqc_mps_pauli_expect": ([_P, _P, _I, _P], _I),
     "aqc_mps_pauli_expect_batch": ([_P, _I, _P, _I, _P], _I),
+    "aqc_pair_tomo_probs": ([_P, _I, _P, _I], _I),
+    "aqc_concurrence_bound_probs": ([_P, _I, _P, _I], _I),
+    "aqc_multinomial_counts": ([_P, _I, _I, _I, ctypes.c_uint64, ctypes.c_uint64, _P, _P], _I),
+    "aqc_tomo_fit": ([_P, _I, _P, _I], _I),
 }
 
 

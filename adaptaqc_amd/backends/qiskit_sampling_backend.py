@@ -155,9 +155,153 @@ class SamplingSimulator:
         return SamplingJob(SamplingResult(counts))
 
 
+def without_classical_operations(circuit):
+    """A copy of ``circuit`` without its measure instructions and classical bits (the reference's
+    co.remove_classical_operations, on a copy)."""
+    qc = circuit.copy()
+    qc.data = [ins for ins in qc.data if ins.operation.name != "measure"]
+    qc.num_clbits = 0
+    return qc
+
+
+def tomography_counts_from_circuits(circuit, qubit_1, qubit_2, simulator, execute_kwargs=None):
+    """The reference's route to a pair's tomography data (entanglement_measures.py:101-135): nine
+    copies of ``circuit`` (without its classical operations), each with the basis rotations of one
+    two-qubit Pauli setting and ``measure(lo -> 0, hi -> 1)``, run through
+    ``simulator.run(copy, **execute_kwargs).result().get_counts()``.  Returns the int64 [9, 4]
+    table: row s = 3 b_hi + b_lo (0 X, 1 Y, 2 Z), column o = 2 o_hi + o_lo (the clbits' values; 0 is
+    the +1 eigenstate).  Bits left of clbit 1 in a key are ignored.  ``circuit`` is not modified."""
+    from ..utils.circuit_operations import add_pauli_measurement_rotations
+
+    lo, hi = sorted((int(qubit_1), int(qubit_2)))
+    if lo == hi:
+        raise ValueError("tomography needs two different qubits")
+    n = circuit.num_qubits
+    base = without_classical_operations(circuit)
+    kwargs = dict(execute_kwargs or {})
+    table = np.zeros((9, 4), dtype=np.int64)
+    for s in range(9):
+        label = ["I"] * n
+        label[n - 1 - hi] = "XYZ"[s // 3]
+        label[n - 1 - lo] = "XYZ"[s % 3]
+        rotated = base.copy()
+        add_pauli_measurement_rotations(rotated, "".join(label))
+        rotated.measure(lo, 0)
+        rotated.measure(hi, 1)
+        counts = simulator.run(rotated, **kwargs).result().get_counts()
+        for key, c in counts.items():
+            bits = key.replace(" ", "").rjust(2, "0")
+            table[s, 2 * int(bits[-2]) + int(bits[-1])] += int(c)
+    return table
+
+
+def concurrence_bound_counts_from_circuits(circuit, qubit_1, qubit_2, simulator, execute_kwargs=None):
+    """The three two-copy circuits of entanglement_measures.py:170-245 on 2 n qubits: the
+    antisymmetric-subspace projector measurement (cx, h, measure) on (qubit_1, n + qubit_1) into
+    clbits 0, 1 and / or on (qubit_2, n + qubit_2) into clbits 2, 3.  Returns the shares
+    (f_pmpm, f_pmi, f_ipm) of the keys "1111", "0011", "1100"."""
+    from ..circuit import QuantumCircuit
+    from ..utils.circuit_operations import add_to_circuit
+
+    n = circuit.num_qubits
+    base = without_classical_operations(circuit)
+    two = QuantumCircuit(2 * n)
+    add_to_circuit(two, base, qubit_subset=list(range(n)))
+    add_to_circuit(two, base, qubit_subset=list(range(n, 2 * n)))
+    kwargs = dict(execute_kwargs or {})
+
+    def projector(qc, q, c0):
+        qc.cx(q, n + q)
+        qc.h(q)
+        qc.measure(q, c0)
+        qc.measure(n + q, c0 + 1)
+
+    shares = []
+    for on_1, on_2, key in ((True, True, "1111"), (True, False, "0011"), (False, True, "1100")):
+        qc = two.copy()
+        if on_1:
+            projector(qc, int(qubit_1), 0)
+        if on_2:
+            projector(qc, int(qubit_2), 2)
+        counts = simulator.run(qc, **kwargs).result().get_counts()
+        counts = {k.replace(" ", "").rjust(4, "0")[-4:]: v for k, v in counts.items()}
+        shares.append(_share(counts, key))
+    return tuple(shares)
+
+
 class QiskitSamplingBackend(AQCBackend):
-    def __init__(self, simulator=None):
+    """``tomography``: how pair entanglement is measured from shots (the ISL method needs it).
+
+    * ``None``: not at all -- ISL with this backend raises at the compiler's construction;
+    * ``"circuits"``: the reference's route, for any simulator that honours the
+      ``run().result().get_counts()`` contract: nine rotated circuits per pair;
+    * ``"device"`` (needs a ``SamplingSimulator``): the state is simulated once, the RDMs of all pairs
+      are taken on the device, and every setting's counts are drawn from the probabilities the RDM
+      fixes (csrc/tomo.hip) -- the law of the counts is that of the nine circuits.
+    """
+
+    TOMOGRAPHY_MODES = (None, "circuits", "device")
+
+    def __init__(self, simulator=None, tomography=None):
+        if tomography not in self.TOMOGRAPHY_MODES:
+            raise ValueError(f"tomography must be one of {self.TOMOGRAPHY_MODES}")
         self.simulator = simulator if simulator is not None else SamplingSimulator()
+        if tomography == "device" and not isinstance(self.simulator, SamplingSimulator):
+            raise TypeError("tomography='device' needs a SamplingSimulator (its cached device state); "
+                            "use tomography='circuits' with other simulators")
+        self.tomography = tomography
+
+    # -- pair tomography ---------------------------------------------------------------
+    def _require_tomography(self):
+        if self.tomography is None:
+            raise NotImplementedError("this QiskitSamplingBackend was built without tomography: pass "
+                                      "tomography='device' or 'circuits'")
+
+    def _seed_and_run(self, kwargs):
+        """(seed, run) of one device sweep: ``seed_simulator`` alone when given, else the
+        simulator's seed and its run counter, which advances once per sweep."""
+        if kwargs.get("seed_simulator") is not None:
+            return int(kwargs["seed_simulator"]), 0
+        seed, run = self.simulator.seed, self.simulator.runs
+        self.simulator.runs += 1
+        return seed, run
+
+    def pair_tomography(self, circuit, pairs, execute_kwargs=None, measure=None):
+        """(rho [npairs, 4, 4], measures [npairs] or None) of the state ``circuit`` prepares, from
+        ``execute_kwargs["shots"]`` shots per Pauli setting.  ``measure``: a name of
+        device.EM_METHOD_CODES.  RDM index 2 bit_hi + bit_lo with hi the pair's larger qubit."""
+        from ..device import entanglement_measures, pair_tomography, tomo_fit
+
+        self._require_tomography()
+        kwargs = dict(execute_kwargs or {})
+        pairs = [(int(a), int(b)) for a, b in pairs]
+        if self.tomography == "device":
+            dev = self.simulator._state(circuit)  # (measures are not part of the cached state's key)
+            rdms = dev.pair_rdms(pairs)
+            seed, run = self._seed_and_run(kwargs)
+            return pair_tomography(rdms, int(kwargs.get("shots", 1024)), seed, run, measure)
+        tables = [tomography_counts_from_circuits(circuit, a, b, self.simulator, kwargs) for a, b in pairs]
+        rho = tomo_fit(np.stack(tables)) if tables else np.zeros((0, 4, 4), dtype=complex)
+        return rho, (None if measure is None else entanglement_measures(rho, measure))
+
+    def concurrence_lower_bounds(self, circuit, pairs, execute_kwargs=None):
+        """The observable concurrence lower bound of every pair (entanglement_measures.py:138-250)."""
+        from ..device import concurrence_lower_bounds
+
+        self._require_tomography()
+        kwargs = dict(execute_kwargs or {})
+        pairs = [(int(a), int(b)) for a, b in pairs]
+        if self.tomography == "device":
+            dev = self.simulator._state(circuit)
+            rdms = dev.pair_rdms(pairs)
+            seed, run = self._seed_and_run(kwargs)
+            return concurrence_lower_bounds(rdms, int(kwargs.get("shots", 1024)), seed, run,
+                                            swap=[a > b for a, b in pairs])
+        out = []
+        for a, b in pairs:
+            pmpm, pmi, ipm = concurrence_bound_counts_from_circuits(circuit, a, b, self.simulator, kwargs)
+            out.append(max(8 * pmpm - 4 * ipm, 8 * pmpm - 4 * pmi))
+        return np.asarray(out, dtype=float)
 
     def evaluate_global_cost(self, compiler):
         """qiskit_sampling_backend.py:24-44: 1 - (share of shots that read all zeros)."""

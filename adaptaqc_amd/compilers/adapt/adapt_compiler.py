@@ -90,10 +90,17 @@ class AdaptCompiler(ApproximateCompiler):
         self.resume_from_layer = None
         self.prev_checkpoint_time_taken = None
         if self.adapt_config.method == "ISL" and self.is_sampling_backend:
-            # (the reference measures pair entanglement there by state tomography of the counts,
-            # entanglement_measures.py:100-180, which this build does not restate)
-            raise NotImplementedError("method 'ISL' needs a statevector or MPS backend: with the shot-sampling "
-                                      "backend use 'expectation', 'random', 'basic' or 'brickwall'")
+            # the reference measures pair entanglement there by state tomography of the counts
+            # (entanglement_measures.py:100-180): the backend says how (tomography="device" / "circuits");
+            # the trailing measures this backend's full circuit carries are classical operations,
+            # which tomography strips
+            if getattr(self.backend, "tomography", None) is None:
+                raise NotImplementedError("method 'ISL' with the shot-sampling backend needs "
+                                          "QiskitSamplingBackend(tomography='device' or 'circuits'); without it "
+                                          "use 'expectation', 'random', 'basic' or 'brickwall'")
+        if comm is not None and self.is_sampling_backend and getattr(self.backend, "tomography", None) is not None:
+            raise NotImplementedError("comm with shot-based tomography: sharding the tomography sweep is "
+                                      "not supported")
         if self.adapt_config.method == "general_gradient":
             if not self.is_aer_mps_backend:
                 raise ValueError("general_gradient method is only implemented for Aer MPS backend")

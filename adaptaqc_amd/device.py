@@ -372,6 +372,119 @@ def entanglement_measures(rdms, method):
     return out
 
 
+# -- shot-based pair tomography (csrc/tomo.hip) -----------------------------------------------------
+# Conventions (include/aqc_hip.h): pair (a, b) as hi = max, lo = min; RDM index 2 bit_hi + bit_lo;
+# basis codes 0 X, 1 Y, 2 Z; setting s = 3 b_hi + b_lo; outcome o = 2 o_hi + o_lo, 0 the +1 eigenstate.
+def _rdm_rows(rdms):
+    return np.ascontiguousarray(np.asarray(rdms, dtype=np.complex128).reshape(-1, 16))
+
+
+def pair_tomo_probs(rdms):
+    """[npairs, 9, 4] outcome probabilities of the nine two-qubit Pauli settings of each 4x4 RDM
+    (aqc_pair_tomo_probs): max(0, <v|rho|v>), not renormalised."""
+    r = _rdm_rows(rdms)
+    out = np.zeros((len(r), 9, 4))
+    if len(r):
+        _lib.check(_lib.lib().aqc_pair_tomo_probs(_lib.ptr(r), len(r), _lib.ptr(out), 0))
+    return out
+
+
+def concurrence_bound_probs(rdms):
+    """[npairs, 3]: P("1111"), P("0011"), P("1100") of the three two-copy circuits of the observable
+    concurrence bound (aqc_concurrence_bound_probs); "0011" belongs to the pair's lower qubit."""
+    r = _rdm_rows(rdms)
+    out = np.zeros((len(r), 3))
+    if len(r):
+        _lib.check(_lib.lib().aqc_concurrence_bound_probs(_lib.ptr(r), len(r), _lib.ptr(out), 0))
+    return out
+
+
+def multinomial_counts(probs, shots, seed, run=0, u=None):
+    """int64[njobs, K] counts of ``shots`` draws from each row of ``probs`` [njobs, K], 2 <= K <= 16
+    (aqc_multinomial_counts).  Job j's shot t uses the uniform of (seed, run, t, j), or ``u[t, j]``
+    when ``u`` [shots, njobs] is given.  Rows need not sum to 1; an all-zero row is an error."""
+    p = np.ascontiguousarray(np.asarray(probs, dtype=np.float64))
+    if p.ndim != 2:
+        raise ValueError("multinomial_counts: probs must be [njobs, K]")
+    njobs, k = p.shape
+    shots = int(shots)
+    up = _uniforms_arg(u, (shots, njobs))
+    out = np.zeros((njobs, k), dtype=np.int64)
+    _lib.check(_lib.lib().aqc_multinomial_counts(_lib.ptr(p), njobs, k, shots, _u64(seed), _u64(run), _lib.ptr(up),
+                                                 _lib.ptr(out)))
+    return out
+
+
+def tomo_fit(counts):
+    """[npairs, 4, 4] density matrices fitted to count tables [npairs, 9, 4] (aqc_tomo_fit): linear
+    inversion, positive-semidefinite rescaling of the eigenvalues, trace 1."""
+    c = np.ascontiguousarray(np.asarray(counts, dtype=np.int64).reshape(-1, 36))
+    out = np.zeros((len(c), 4, 4), dtype=np.complex128)
+    if len(c):
+        _lib.check(_lib.lib().aqc_tomo_fit(_lib.ptr(c), len(c), _lib.ptr(out), 0))
+    return out
+
+
+def pair_tomography(rdms, shots, seed, run=0, method=None, timings=None):
+    """Tomography of every pair as one launch chain on device buffers: probabilities of the nine
+    settings -> ``shots`` draws per setting (job index pair 9 + s) -> fit -> measure.  Returns
+    (rho [npairs, 4, 4], measures [npairs] or None when ``method`` is None).  ``timings``: a dict
+    that receives the wall-clock seconds of each stage (every stage ends on a stream
+    synchronisation)."""
+    import time
+
+    import torch
+
+    r = _rdm_rows(rdms)
+    npairs = len(r)
+    if npairs == 0:
+        return np.zeros((0, 4, 4), dtype=np.complex128), (None if method is None else np.zeros(0))
+    l = _lib.lib()
+    dev = torch.device("cuda", _lib.device_index())
+    drdm = torch.from_numpy(r.view(np.float64)).to(dev)
+    probs = torch.empty(npairs * 36, dtype=torch.float64, device=dev)
+    counts = torch.empty(npairs * 36, dtype=torch.int64, device=dev)
+    rho = torch.empty(npairs * 32, dtype=torch.float64, device=dev)
+    meas = torch.empty(npairs, dtype=torch.float64, device=dev)
+    # (the library's stream waits for the upload queued on torch's; each call below returns after
+    # its own stream synchronisation, so torch's reads afterwards need no further ordering)
+    _lib.check(l.aqc_stream_wait(ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
+    def p(t):
+        return ctypes.c_void_p(t.data_ptr())
+
+    def stage(name, call):
+        t0 = time.perf_counter()
+        _lib.check(call())
+        if timings is not None:
+            timings[name] = timings.get(name, 0.0) + time.perf_counter() - t0
+
+    stage("probs", lambda: l.aqc_pair_tomo_probs(p(drdm), npairs, p(probs), 1))
+    stage("counts", lambda: l.aqc_multinomial_counts(p(probs), npairs * 9, 4, int(shots), _u64(seed), _u64(run), None,
+                                                     p(counts)))
+    stage("fit", lambda: l.aqc_tomo_fit(p(counts), npairs, p(rho), 1))
+    if method is not None:
+        code = EM_METHOD_CODES[method]
+        stage("measure", lambda: l.aqc_entanglement_measures(p(rho), npairs, code, p(meas), 1))
+    out = rho.cpu().numpy().view(np.complex128).reshape(npairs, 4, 4)
+    return out, (meas.cpu().numpy() if method is not None else None)
+
+
+def concurrence_lower_bounds(rdms, shots, seed, run=0, swap=None):
+    """The observable concurrence lower bound max(8 f_pmpm - 4 f_ipm, 8 f_pmpm - 4 f_pmi) of every
+    pair from three binomial jobs a pair (K = 2, job index pair 3 + c; c = 0 pmpm, 1 pmi, 2 ipm).
+    ``swap[pair]``: qubit_1 is the pair's higher qubit (pmi and ipm change places)."""
+    pr = concurrence_bound_probs(rdms)
+    if len(pr) == 0:
+        return np.zeros(0)
+    if swap is not None:
+        sw = np.asarray(swap, dtype=bool)
+        pr[sw] = pr[sw][:, [0, 2, 1]]
+    jobs = np.stack([pr.reshape(-1), 1.0 - pr.reshape(-1)], axis=1)
+    f = multinomial_counts(jobs, shots, seed, run)[:, 0].reshape(-1, 3) / float(shots)
+    return np.maximum(8 * f[:, 0] - 4 * f[:, 2], 8 * f[:, 0] - 4 * f[:, 1])
+
+
 def copy_batch(dst, src):
     """dst[s] <- src[s] for every state in one launch (per-evaluation reload of a cached MPS)."""
     if len(dst) != len(src):

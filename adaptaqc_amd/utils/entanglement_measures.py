@@ -22,8 +22,11 @@ log-negativity :299-306).  ``pair_entanglement_measures`` is the batched form th
 sweep uses (adapt_compiler.py:955-976): one device state, every pair's RDM in one launch chain,
 every measure in one launch.
 
-Not on this path (raise NotImplementedError): the observable lower bound (:101-242, needs shot
-sampling) and quantum state tomography (:101-136).
+With a ``QiskitSamplingBackend`` built with ``tomography="device"`` or ``"circuits"`` the density
+matrix comes from shot-based state tomography (:101-136) and the observable concurrence lower bound
+(:138-250) from its three two-copy measurements -- drawn on the device from the pairs' RDMs
+(csrc/tomo.hip), or through the reference's rotated circuits.  The lower bound keeps raising
+NotImplementedError on the statevector and MPS backends, as the reference says it must.
 """
 import itertools
 import logging
@@ -59,10 +62,16 @@ def _kind(backend):
     return None
 
 
+def _sampling(backend):
+    from ..backends.qiskit_sampling_backend import QiskitSamplingBackend
+
+    return isinstance(backend, QiskitSamplingBackend)
+
+
 def _measure_name(method):
     if method == EM_OBSERVABLE_CONCURRENCE_LOWER_BOUND:
-        raise NotImplementedError("the observable concurrence lower bound needs shot sampling, which is "
-                                  "outside the MI355X overlap/gradient path")
+        raise NotImplementedError("the observable concurrence lower bound needs a shot-sampling backend "
+                                  "(QiskitSamplingBackend with tomography set)")
     if method not in _CODES:
         raise ValueError("Invalid entanglement measure method")
     return _CODES[method]
@@ -71,6 +80,13 @@ def _measure_name(method):
 def calculate_entanglement_measure(method, circuit, qubit_1, qubit_2, backend, backend_options=None,
                                    execute_kwargs=None, mps=None):
     """Entanglement between two qubits of the state prepared by ``circuit`` (reference :39-98)."""
+    if _sampling(backend):
+        if method == EM_OBSERVABLE_CONCURRENCE_LOWER_BOUND:
+            return measure_concurrence_lower_bound(circuit, qubit_1, qubit_2, backend, backend_options, execute_kwargs)
+        if method not in _CODES:
+            raise ValueError("Invalid entanglement measure method")
+        _, vals = backend.pair_tomography(circuit, [(qubit_1, qubit_2)], execute_kwargs, _CODES[method])
+        return float(vals[0])
     name = _measure_name(method)
     kind = _kind(backend)
     if kind == "sv":
@@ -99,6 +115,20 @@ def pair_entanglement_measures(method, compiler, pairs, comm=None):
     every rank the whole list."""
     from ..sharding import sharded_pair_scores
 
+    if _sampling(compiler.backend):
+        # one simulation, one all-pair RDM chain, then counts, fit and measure of every pair
+        if method != EM_OBSERVABLE_CONCURRENCE_LOWER_BOUND and method not in _CODES:
+            raise ValueError("Invalid entanglement measure method")
+        if comm is not None:
+            raise NotImplementedError("sharding the tomography sweep is not supported")
+        if not pairs:
+            return []
+        if method == EM_OBSERVABLE_CONCURRENCE_LOWER_BOUND:
+            vals = compiler.backend.concurrence_lower_bounds(compiler.full_circuit, pairs, compiler.execute_kwargs)
+        else:
+            _, vals = compiler.backend.pair_tomography(compiler.full_circuit, pairs, compiler.execute_kwargs,
+                                                       _CODES[method])
+        return [float(x) for x in vals]
     name = _measure_name(method)
     if not pairs:
         return []
@@ -157,8 +187,21 @@ def partial_transpose(density_matrix, wrt=1):
 
 def measure_concurrence_lower_bound(circuit, qubit_1, qubit_2, backend, backend_options=None,
                                     execute_kwargs=None):
-    raise NotImplementedError("the observable concurrence lower bound needs shot sampling")
+    """reference :138-250: max(8 f_pmpm - 4 f_ipm, 8 f_pmpm - 4 f_pmi) from the shares of "1111",
+    "1100" and "0011" in the three two-copy measurements.  ``backend``: a QiskitSamplingBackend with
+    tomography set; statevector and MPS backends cannot run it."""
+    if not _sampling(backend):
+        raise NotImplementedError("the observable concurrence lower bound needs a shot-sampling backend")
+    return float(backend.concurrence_lower_bounds(circuit, [(qubit_1, qubit_2)], execute_kwargs)[0])
 
 
-def perform_quantum_tomography(circuit, qubit_1, qubit_2, backend, backend_options=None, execute_kwargs=None):
-    raise NotImplementedError("quantum state tomography needs a shot-sampling backend")
+def perform_quantum_tomography(circuit, qubit_1, qubit_2, simulator, backend_options=None, execute_kwargs=None):
+    """reference :101-135: the 4x4 density matrix of (qubit_1, qubit_2) fitted to shot counts (index
+    2 bit_hi + bit_lo, hi the larger qubit).  A ``SamplingSimulator`` takes the device route (its
+    state's RDM, then counts, fit); any other simulator the nine rotated circuits."""
+    from ..backends.qiskit_sampling_backend import QiskitSamplingBackend, SamplingSimulator
+
+    mode = "device" if isinstance(simulator, SamplingSimulator) else "circuits"
+    rho, _ = QiskitSamplingBackend(simulator, tomography=mode).pair_tomography(circuit, [(qubit_1, qubit_2)],
+                                                                               execute_kwargs)
+    return np.array(rho[0])

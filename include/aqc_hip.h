@@ -173,6 +173,39 @@ int aqc_sv_pauli_expect(aqc_sv_t h, const uint64_t* xmask, const uint64_t* zmask
 int aqc_mps_pauli_expect(aqc_mps_t h, const uint8_t* codes, int nterms, double* out);
 int aqc_mps_pauli_expect_batch(aqc_mps_t* hs, int nstates, const uint8_t* codes, int nterms, double* out);
 
+/* ---- shot-based pair tomography: replaces the per-pair circuits of entanglement_measures.py:101-135
+   (perform_quantum_tomography) and :138-250 (measure_concurrence_lower_bound) ----
+   Each of those circuits measures two qubits, so its counts are a multinomial draw that the pair's
+   4x4 reduced density matrix fixes: the state is simulated once, the RDMs come from the pair-RDM
+   entry points above, and counts, fit and measure of every pair follow in a few launches.
+   Conventions: pair (a, b) as hi = max, lo = min; RDM index 2 bit_hi + bit_lo; basis codes 0 X, 1 Y,
+   2 Z; setting s = 3 b_hi + b_lo; outcome o = 2 o_hi + o_lo with 0 the +1 eigenstate -- X: (|0> +- |1>)
+   / sqrt 2, Y: (|0> +- i|1>) / sqrt 2 (which sdg then h maps onto |0>, |1>), Z: |0>, |1>.
+   rdms / out (and counts / out_rdms of aqc_tomo_fit) in device memory when on_device. */
+/* out[(pair 9 + s) 4 + o] = max(0, <v|rho|v>), v the product eigenvector of (s, o).  Not
+   renormalised (a truncated MPS has Tr rho < 1; the draw divides by the total). */
+int aqc_pair_tomo_probs(const double* rdms, int npairs, double* out, int on_device);
+/* out[3 pair + c]: the key probabilities of the three two-copy circuits, c = 0: P("1111") =
+   (1 - Tr rho_1^2 - Tr rho_2^2 + Tr rho_12^2) / 4, 1: P("0011") = (1 - Tr rho_1^2) / 2, 2: P("1100") =
+   (1 - Tr rho_2^2) / 2, each clamped at 0; rho_1 / rho_2: the marginal of the pair's lower / higher qubit. */
+int aqc_concurrence_bound_probs(const double* rdms, int npairs, double* out, int on_device);
+/* counts[job K + k] (int64) of nshots draws from job's K probabilities (2 <= K <= 16), nshots in
+   1 .. 2^30.  Job j's shot t uses sample_uniform(seed, run, t, j) (counter (t lo, t hi, j, run)), or
+   u[t njobs + j] when u is not null (the layout of aqc_sample_uniforms(seed, run, nshots, njobs)).
+   Rule, with C_k the in-order inclusive sums and P = C_{K-1}: the smallest k with C_k > u P; where
+   rounding leaves none, the last k with p_k > 0 (the statevector sampler's rule).  A negative or
+   non-finite probability, or P = 0: AQC_ERR_ARG.  probs, u and counts may each be host or device
+   memory (the runtime tells which).  Integer sums throughout: the counts do not depend on the launch shape. */
+int aqc_multinomial_counts(const double* probs, int njobs, int K, int nshots, uint64_t seed, uint64_t run,
+                           const double* u, int64_t* counts);
+/* counts[pair][9][4] -> out_rdms[pair][4][4]: f = counts / (the setting's total; zero: AQC_ERR_ARG),
+   linear inversion rho = 1/4 sum T[P][Q] P (x) Q (T[I][I] = 1; T of two letters from their setting;
+   T[P][I], T[I][Q] the signed marginal averaged over the three settings measuring it), then the
+   positive-semidefinite rescaling of Smolin, Gambetta and Smith (PRL 108, 070502: eigenvalues in
+   descending order, a = 0, i = 4; while mu_i + a / i < 0: a += mu_i, mu_i = 0, i -= 1; lambda_j =
+   mu_j + a / i for j <= i) and division by the trace. */
+int aqc_tomo_fit(const int64_t* counts, int npairs, double* out_rdms, int on_device);
+
 /* move_all_qubits_to_sorted_ordering (done implicitly by every measurement below). */
 int aqc_mps_sort(aqc_mps_t h);
 int aqc_mps_sort_batch(aqc_mps_t* hs, int nstates);
