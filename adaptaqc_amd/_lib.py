@@ -39,6 +39,7 @@ EXPORTS = (
     "aqc_comm_unique_id", "aqc_comm_init", "aqc_comm_destroy", "aqc_comm_rank", "aqc_allgather_f64",
     "aqc_allgather_f64_host", "aqc_allreduce_max_f64", "aqc_svd_gram_big_stats", "aqc_svd_gram_big_ticks",
     "aqc_gb_set_spin_limit", "aqc_gb_set_tail", "aqc_gb_set_stages", "aqc_debug_hog", "aqc_pool_stats",
+    "aqc_scratch_stats",
     "aqc_env_fallbacks", "aqc_env_set_single", "aqc_env_set_spin_limit",
     "aqc_sv_sample", "aqc_mps_sample", "aqc_sample_uniforms",
     "aqc_sv_pauli_expect", "aqc_mps_pauli_expect", "aqc_mps_pauli_expect_batch",
@@ -144,6 +145,7 @@ _SIGS = {
     "aqc_gb_set_stages": ([_I], _I),
     "aqc_debug_hog": ([_I, _D], _I),
     "aqc_pool_stats": ([_P], _I),
+    "aqc_scratch_stats": ([_P], _I),
     "aqc_sv_sample": ([_P, _I, ctypes.c_uint64, ctypes.c_uint64, _P, _P], _I),
     "aqc_mps_sample": ([_P, _I, ctypes.c_uint64, ctypes.c_uint64, _P, _P], _I),
     "aqc_sample_uniforms": ([ctypes.c_uint64, ctypes.c_uint64, _I, _I, _P], _I),

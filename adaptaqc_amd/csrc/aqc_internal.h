@@ -166,12 +166,59 @@ __device__ __forceinline__ double group_sum(double v) {
 }
 
 // ---- teardown ----------------------------------------------------------------------------
-// Lazily created HIP objects (side streams, events, cached buffer sets) register a cleanup here
+// Lazily created HIP objects (side streams, events, the memory pool) register a cleanup here
 // when they are first created; aqc_finalize synchronises every device the library touched, runs
-// the cleanups (newest first) and forgets them, so the objects are recreated on next use.  The
-// Python loader calls aqc_finalize from atexit, before the HIP runtime's own teardown.
+// the cleanups (newest first) and forgets them, so the objects are recreated on next use, then
+// releases the per-device scratch tables (below).  The Python loader calls aqc_finalize from
+// atexit, before the HIP runtime's own teardown.
 void on_finalize(void (*fn)());
 void note_device(int dev);
+
+// ---- per-device scratch ------------------------------------------------------------------
+// The staging every host-side entry point needs (job tables, partial sums, pinned results) lives in
+// grow-only buffers, one per device, that aqc_finalize frees.  A DevScratch is one such buffer: a
+// device block, an optional pinned host block, and an event for callers that reuse it while work
+// that read it may still be queued.  It allocates with hipMalloc / hipHostMalloc, not through the
+// dev_alloc pool below.  No locking of its own: the few sites shared between threads hold a mutex.
+inline size_t up256(size_t b) { return (b + 255) / 256 * 256; }
+
+struct DevScratch {
+  char* dev = nullptr;
+  size_t cap = 0;
+  char* host = nullptr;
+  size_t hcap = 0;
+  hipEvent_t done = nullptr;
+  bool pending = false;
+
+  // Room for dev_bytes on the device and host_bytes pinned; a side that is too small grows to
+  // max(need, 2 x its size) and loses its contents (*regrown: the device side did).  The caller
+  // has made sure that no queued work still uses the buffer.  On failure the side that failed is
+  // left {nullptr, 0}.
+  int ensure(size_t dev_bytes, size_t host_bytes = 0, bool* regrown = nullptr);
+  int wait();               // until the work marked last is done
+  int mark(hipStream_t s);  // the work queued on s so far uses the buffer
+  void release();
+};
+
+// One T per device, T::release()d by aqc_finalize.
+void register_table(void* table, void (*release_all)(void*));
+template <typename T>
+struct PerDevice {
+  T entry[64];
+  bool registered = false;
+  T& here() {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (!registered) {
+      register_table(this, [](void* t) {
+        for (T& e : static_cast<PerDevice*>(t)->entry) e.release();
+      });
+      registered = true;
+    }
+    note_device(dev);
+    return entry[dev & 63];
+  }
+};
 
 // Host -> device copy of a pinned (hipHostMalloc) staging buffer on `st`, done by a kernel that
 // reads the host memory over the bus: the stream's next kernel then depends on a kernel, not on a

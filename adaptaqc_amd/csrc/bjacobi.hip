@@ -617,68 +617,46 @@ __global__ __launch_bounds__(1024) void k_bj_final(const TwoSiteJob* __restrict_
   if (lane == 0) j.sig[col] = sqrt(n2);
 }
 
-struct BJBuffers {
-  BJState* st = nullptr;
-  int* ndone = nullptr;  // device counter
-  int* host = nullptr;   // pinned read-back
-  int cap = 0;
-};
-
-BJBuffers g_bj_buffers;
-void release_bj_buffers() {
-  BJBuffers& b = g_bj_buffers;
-  if (b.st) (void)hipFree(b.st);
-  if (b.ndone) (void)hipFree(b.ndone);
-  if (b.host) (void)hipHostFree(b.host);
-  b = BJBuffers();
-}
-BJBuffers& bj_buffers() {
-  aqc::on_finalize(release_bj_buffers);
-  return g_bj_buffers;
-}
+// per job state, then the device counter of converged jobs; its pinned read-back
+aqc::PerDevice<aqc::DevScratch> g_bj_buffers;
 
 template <int MAXR>
 int run_block_jacobi(const TwoSiteJob* jobs, int nj, int cap_max, hipStream_t stream) {
-  BJBuffers& b = bj_buffers();
-  if (b.cap < nj) {
-    AQC_HIP_CHECK(hipStreamSynchronize(stream));
-    if (b.st) hipFree(b.st);
-    if (b.ndone) hipFree(b.ndone);
-    if (b.host) hipHostFree(b.host);
-    b.st = nullptr, b.ndone = nullptr, b.host = nullptr, b.cap = 0;
-    AQC_HIP_CHECK(hipMalloc(&b.st, sizeof(BJState) * nj));
-    AQC_HIP_CHECK(hipMalloc(&b.ndone, sizeof(int)));
-    AQC_HIP_CHECK(hipHostMalloc(&b.host, sizeof(int)));
-    b.cap = nj;
-  }
-  AQC_HIP_CHECK(hipMemsetAsync(b.st, 0, sizeof(BJState) * nj, stream));
-  AQC_HIP_CHECK(hipMemsetAsync(b.ndone, 0, sizeof(int), stream));
+  aqc::DevScratch& buf = g_bj_buffers.here();
+  const size_t sb = up256(sizeof(BJState) * nj);
+  if (buf.cap < sb + sizeof(int)) AQC_HIP_CHECK(hipStreamSynchronize(stream));
+  if (int rc = buf.ensure(sb + sizeof(int), sizeof(int))) return rc;
+  BJState* bst = (BJState*)buf.dev;
+  int* ndone = (int*)(buf.dev + sb);
+  int* hdone = (int*)buf.host;
+  AQC_HIP_CHECK(hipMemsetAsync(bst, 0, sizeof(BJState) * nj, stream));
+  AQC_HIP_CHECK(hipMemsetAsync(ndone, 0, sizeof(int), stream));
   const int L = 2 * cap_max;
   int nb = (L + kB - 1) / kB;
   nb += nb & 1;
   const size_t lds = MAXR > 8 ? 0 : (size_t)kB * 64 * MAXR * sizeof(double2);
-  hipLaunchKernelGGL(k_bj_init, dim3(nj), dim3(1024), 0, stream, jobs, b.st);
+  hipLaunchKernelGGL(k_bj_init, dim3(nj), dim3(1024), 0, stream, jobs, bst);
   AQC_CHECK_LAUNCH();
   for (int sweep = 0; sweep < kMaxSweepsBJ; ++sweep) {
     constexpr bool kFull = MAXR > 8;  // 2 chi > 512: the intra block would not fit the LDS
     if constexpr (!kFull) {
-      hipLaunchKernelGGL((k_bj_intra<MAXR>), dim3(nb, nj), dim3(512), lds, stream, jobs, b.st);
+      hipLaunchKernelGGL((k_bj_intra<MAXR>), dim3(nb, nj), dim3(512), lds, stream, jobs, bst);
       AQC_CHECK_LAUNCH();
     }
     for (int r = 0; r < nb - 1; ++r) {
-      hipLaunchKernelGGL((k_bj_pair<MAXR, kFull>), dim3(nb / 2, nj), dim3(256), kPairLdsBytes, stream, jobs, b.st, r,
+      hipLaunchKernelGGL((k_bj_pair<MAXR, kFull>), dim3(nb / 2, nj), dim3(256), kPairLdsBytes, stream, jobs, bst, r,
                          nb);
       AQC_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(k_bj_sweep_end, dim3(nj), dim3(64), 0, stream, b.st, b.ndone);
+    hipLaunchKernelGGL(k_bj_sweep_end, dim3(nj), dim3(64), 0, stream, bst, ndone);
     AQC_CHECK_LAUNCH();
     if (sweep >= 2) {
-      AQC_HIP_CHECK(hipMemcpyAsync(b.host, b.ndone, sizeof(int), hipMemcpyDeviceToHost, stream));
+      AQC_HIP_CHECK(hipMemcpyAsync(hdone, ndone, sizeof(int), hipMemcpyDeviceToHost, stream));
       AQC_HIP_CHECK(hipStreamSynchronize(stream));
-      if (*b.host >= nj) break;
+      if (*hdone >= nj) break;
     }
   }
-  hipLaunchKernelGGL((k_bj_final<MAXR>), dim3(nb, nj), dim3(1024), 0, stream, jobs, b.st);
+  hipLaunchKernelGGL((k_bj_final<MAXR>), dim3(nb, nj), dim3(1024), 0, stream, jobs, bst);
   AQC_CHECK_LAUNCH();
   return AQC_OK;
 }

@@ -69,6 +69,67 @@ void note_device(int dev) {
 }
 
 namespace {
+std::vector<std::pair<void*, void (*)(void*)>> g_tables;  // registered PerDevice tables (g_fin_mutex)
+std::atomic<long long> g_scr_bytes[2], g_scr_allocs[2];   // [0] device, [1] pinned
+}  // namespace
+
+void register_table(void* table, void (*release_all)(void*)) {
+  std::lock_guard<std::mutex> lk(g_fin_mutex);
+  g_tables.emplace_back(table, release_all);
+}
+
+int DevScratch::ensure(size_t dev_bytes, size_t host_bytes, bool* regrown) {
+  if (regrown) *regrown = false;
+  if (dev_bytes > cap) {
+    const size_t want = std::max(dev_bytes, 2 * cap);
+    if (dev) (void)hipFree(dev);
+    g_scr_bytes[0] -= (long long)cap;
+    dev = nullptr;
+    cap = 0;
+    if (regrown) *regrown = true;
+    AQC_HIP_CHECK(hipMalloc((void**)&dev, want));
+    cap = want;
+    g_scr_bytes[0] += (long long)want;
+    ++g_scr_allocs[0];
+  }
+  if (host_bytes > hcap) {
+    const size_t want = std::max(host_bytes, 2 * hcap);
+    if (host) (void)hipHostFree(host);
+    g_scr_bytes[1] -= (long long)hcap;
+    host = nullptr;
+    hcap = 0;
+    AQC_HIP_CHECK(hipHostMalloc((void**)&host, want, hipHostMallocDefault));
+    hcap = want;
+    g_scr_bytes[1] += (long long)want;
+    ++g_scr_allocs[1];
+  }
+  return AQC_OK;
+}
+
+int DevScratch::wait() {
+  if (!pending) return AQC_OK;
+  pending = false;
+  AQC_HIP_CHECK(hipEventSynchronize(done));
+  return AQC_OK;
+}
+
+int DevScratch::mark(hipStream_t s) {
+  if (!done) AQC_HIP_CHECK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+  AQC_HIP_CHECK(hipEventRecord(done, s));
+  pending = true;
+  return AQC_OK;
+}
+
+void DevScratch::release() {
+  if (dev) (void)hipFree(dev);
+  if (host) (void)hipHostFree(host);
+  if (done) (void)hipEventDestroy(done);
+  g_scr_bytes[0] -= (long long)cap;
+  g_scr_bytes[1] -= (long long)hcap;
+  *this = DevScratch();
+}
+
+namespace {
 std::mutex g_pool_mutex;
 struct PoolKey {
   int dev;
@@ -283,6 +344,15 @@ int aqc_debug_hog(int nblocks, double ms) {
   return AQC_OK;
 }
 
+int aqc_scratch_stats(double* out) {
+  AQC_REQUIRE(out, "aqc_scratch_stats: null out");
+  for (int k = 0; k < 2; ++k) {
+    out[k] = (double)aqc::g_scr_bytes[k].load();
+    out[2 + k] = (double)aqc::g_scr_allocs[k].load();
+  }
+  return AQC_OK;
+}
+
 int aqc_pool_stats(double* out) {
   AQC_REQUIRE(out, "aqc_pool_stats: null out");
   std::lock_guard<std::mutex> lk(aqc::g_pool_mutex);
@@ -334,6 +404,10 @@ int aqc_finalize(void) {
     fin.swap(aqc::g_fin);
   }
   for (auto it = fin.rbegin(); it != fin.rend(); ++it) (*it)();
+  {
+    std::lock_guard<std::mutex> lk(aqc::g_fin_mutex);
+    for (auto& t : aqc::g_tables) t.second(t.first);  // (registered for good: the tables are statics)
+  }
   return rc;
 }
 

@@ -909,36 +909,10 @@ __global__ void k_ent_measure(const cplx* __restrict__ rdms, int count, int meth
   out[p] = v;
 }
 
-struct RdmBuffers {
-  void* dev = nullptr;
-  size_t cap = 0;
-};
-
-RdmBuffers g_rbuf[64];
-void release_rbuf() {
-  for (auto& b : g_rbuf) {
-    if (b.dev) (void)hipFree(b.dev);
-    b = RdmBuffers();
-  }
-}
-RdmBuffers& rbuf() {
-  int dev = 0;
-  hipGetDevice(&dev);
-  aqc::on_finalize(release_rbuf);
-  return g_rbuf[dev];
-}
-
-int ensure(RdmBuffers& b, size_t need) {
-  if (need > b.cap) {
-    if (b.dev) hipFree(b.dev);
-    b.cap = std::max(need, 2 * b.cap);
-    AQC_HIP_CHECK(hipMalloc(&b.dev, b.cap));
-  }
-  return AQC_OK;
-}
+aqc::PerDevice<aqc::DevScratch> g_rbuf;  // jobs, environments and results of every entry point here
 
 // Counter / error words behind the jobs of an environment launch: 32 words per chain, one error word.
-size_t env_sync_bytes(int ns) { return (((size_t)ns * 2 * 32 + 32) * sizeof(unsigned) + 255) / 256 * 256; }
+size_t env_sync_bytes(int ns) { return aqc::up256(((size_t)ns * 2 * 32 + 32) * sizeof(unsigned)); }
 
 // Output columns per workgroup of the split environment chains for a capacity, or 0 where the
 // chains run one workgroup each (k_rdm_env).  Each split kernel's slices of tmpL / tmpR are sized for
@@ -1046,14 +1020,14 @@ int aqc::mps_right_envs(aqc_mps_s* h, size_t extra_bytes, const cplx** renv, voi
   const int n = h->d.n, cap = h->d.cap;
   const size_t cc = (size_t)cap * cap;
   const size_t per_state = (2 * (size_t)(n + 1) * cc + 4 * cc) * sizeof(cplx);
-  const size_t jb = ((sizeof(RdmJob) + 255) / 256) * 256;
+  const size_t jb = aqc::up256(sizeof(RdmJob));
   hipStream_t st = aqc::mps_stream();
-  RdmBuffers& rb = rbuf();
+  aqc::DevScratch& rb = g_rbuf.here();
   AQC_HIP_CHECK(hipStreamSynchronize(st));
   const size_t sb = env_sync_bytes(1);
-  int rc = ensure(rb, jb + per_state + sb + extra_bytes + 1024);
+  int rc = rb.ensure(jb + per_state + sb + extra_bytes + 1024);
   if (rc != AQC_OK) return rc;
-  char* base = (char*)rb.dev;
+  char* base = rb.dev;
   RdmJob* djobs = (RdmJob*)base;
   cplx* work = (cplx*)(base + jb);
   void* dsync = base + jb + per_state;
@@ -1096,14 +1070,14 @@ int aqc::mps_envs_batch(aqc_mps_s** hs, int ns, size_t extra_bytes, const char* 
   const int n = hs[0]->d.n, cap = hs[0]->d.cap;
   const size_t cc = (size_t)cap * cap;
   const size_t per_state = (2 * (size_t)(n + 1) * cc + 4 * cc) * sizeof(cplx);
-  const size_t jb = (((size_t)ns * sizeof(RdmJob) + 255) / 256) * 256;
+  const size_t jb = aqc::up256((size_t)ns * sizeof(RdmJob));
   hipStream_t st = aqc::mps_stream();
-  RdmBuffers& rb = rbuf();
+  aqc::DevScratch& rb = g_rbuf.here();
   AQC_HIP_CHECK(hipStreamSynchronize(st));
   const size_t sb = env_sync_bytes(ns);
-  int rc = ensure(rb, jb + (size_t)ns * per_state + sb + extra_bytes + 1024);
+  int rc = rb.ensure(jb + (size_t)ns * per_state + sb + extra_bytes + 1024);
   if (rc != AQC_OK) return rc;
-  char* base = (char*)rb.dev;
+  char* base = rb.dev;
   RdmJob* djobs = (RdmJob*)base;
   cplx* work = (cplx*)(base + jb);
   void* dsync = base + jb + (size_t)ns * per_state;
@@ -1168,16 +1142,16 @@ int aqc_mps_pair_rdms_batch(aqc_mps_t* hs, int ns, const int* pairs, int npairs,
   const size_t cc = (size_t)cap * cap;
   const size_t per_state =
       (2 * (size_t)(n + 1) * cc + 4 * cc + 6 * (size_t)n * cc + 12 * (size_t)na * cc + (size_t)n * n * 16) * sizeof(cplx);
-  const size_t jb = ((ns * sizeof(RdmJob) + 255) / 256) * 256;
-  const size_t pb = ((2 * npairs * sizeof(int) + na * sizeof(int) + 255) / 256) * 256;
+  const size_t jb = aqc::up256(ns * sizeof(RdmJob));
+  const size_t pb = aqc::up256(2 * npairs * sizeof(int) + na * sizeof(int));
   const size_t ob = out_is_device ? 0 : (size_t)ns * npairs * 16 * sizeof(cplx);
   hipStream_t st = aqc::mps_stream();
-  RdmBuffers& rb = rbuf();
+  aqc::DevScratch& rb = g_rbuf.here();
   AQC_HIP_CHECK(hipStreamSynchronize(st));
   const size_t sb = env_sync_bytes(ns);
-  rc = ensure(rb, jb + pb + ob + ns * per_state + sb + 1024);
+  rc = rb.ensure(jb + pb + ob + ns * per_state + sb + 1024);
   if (rc != AQC_OK) return rc;
-  char* base = (char*)rb.dev;
+  char* base = rb.dev;
   RdmJob* djobs = (RdmJob*)base;
   void* dsync = base + jb + pb + ob + ns * per_state;
   int* dpairs = (int*)(base + jb);
@@ -1250,15 +1224,15 @@ int aqc_mps_z_all_batch(aqc_mps_t* hs, int ns, double* out) {
   if (rc != AQC_OK) return rc;
   const size_t cc = (size_t)cap * cap;
   const size_t per_state = (2 * (size_t)(n + 1) * cc + 4 * cc + 6 * (size_t)n * cc) * sizeof(cplx);
-  const size_t jb = ((ns * sizeof(RdmJob) + 255) / 256) * 256;
-  const size_t ob = (((size_t)ns * n * sizeof(double) + 255) / 256) * 256;
+  const size_t jb = aqc::up256(ns * sizeof(RdmJob));
+  const size_t ob = aqc::up256((size_t)ns * n * sizeof(double));
   hipStream_t st = aqc::mps_stream();
-  RdmBuffers& rb = rbuf();
+  aqc::DevScratch& rb = g_rbuf.here();
   AQC_HIP_CHECK(hipStreamSynchronize(st));
   const size_t sb = env_sync_bytes(ns);
-  rc = ensure(rb, jb + ob + ns * per_state + sb + 1024);
+  rc = rb.ensure(jb + ob + ns * per_state + sb + 1024);
   if (rc != AQC_OK) return rc;
-  char* base = (char*)rb.dev;
+  char* base = rb.dev;
   RdmJob* djobs = (RdmJob*)base;
   double* dout = (double*)(base + jb);
   void* dsync = base + jb + ob + ns * per_state;
@@ -1381,17 +1355,17 @@ int aqc_mps_z_sum_batch(aqc_mps_t base, aqc_mps_t* hs, int ns, double* out) {
       nwin_ch += 1 + (w > nl ? 1 : 0);
     }
     const int nch = nbase + nwin_ch;
-    const size_t jb = ((nch * sizeof(ZJob) + 255) / 256) * 256;
-    const size_t zb = ((win.size() * sizeof(ZSumJob) + 255) / 256) * 256;
-    const size_t ob = ((win.size() * sizeof(double) + 255) / 256) * 256;
-    const size_t sb = ((((size_t)nch * 32 + 32) * sizeof(unsigned) + 255) / 256) * 256;
+    const size_t jb = aqc::up256(nch * sizeof(ZJob));
+    const size_t zb = aqc::up256(win.size() * sizeof(ZSumJob));
+    const size_t ob = aqc::up256(win.size() * sizeof(double));
+    const size_t sb = aqc::up256(((size_t)nch * 32 + 32) * sizeof(unsigned));
     const size_t tb = (size_t)nch * 4 * cc * sizeof(cplx);
     const size_t wb = wsteps * pair * sizeof(cplx);
-    RdmBuffers& rb = rbuf();
+    aqc::DevScratch& rb = g_rbuf.here();
     AQC_HIP_CHECK(hipStreamSynchronize(st));
-    rc = ensure(rb, jb + zb + ob + sb + tb + wb + 1024);
+    rc = rb.ensure(jb + zb + ob + sb + tb + wb + 1024);
     if (rc != AQC_OK) return rc;
-    char* b = (char*)rb.dev;
+    char* b = rb.dev;
     ZJob* dj = (ZJob*)b;
     ZSumJob* dz = (ZSumJob*)(b + jb);
     double* dout = (double*)(b + jb + zb);

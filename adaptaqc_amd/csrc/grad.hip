@@ -833,60 +833,15 @@ __global__ __launch_bounds__(kT) void k_product_fit(const FitJob* __restrict__ j
 // buffer pairs, each guarded by an event recorded after the launches that read it, so a call
 // packs its constants into one pinned buffer and issues ONE asynchronous copy instead of draining
 // the stream and issuing blocking hipMemcpys.
-struct GradBuffers {
-  void* dev = nullptr;
-  size_t cap = 0;
-  char* host = nullptr;
-  size_t hcap = 0;
-  hipEvent_t done = nullptr;
-  bool pending = false;
-};
-
 struct GradRing {
   std::mutex mu;
-  GradBuffers b[2];
+  aqc::DevScratch b[2];
   int next = 0;
+  void release() {
+    for (auto& s : b) s.release();
+  }
 };
-
-GradRing g_gring[64];
-void release_gring() {
-  for (auto& r : g_gring)
-    for (auto& b : r.b) {
-      if (b.done) (void)hipEventDestroy(b.done);
-      if (b.dev) (void)hipFree(b.dev);
-      if (b.host) (void)hipHostFree(b.host);
-      b.done = nullptr, b.dev = nullptr, b.host = nullptr;
-      b.cap = b.hcap = 0;
-      b.pending = false;
-    }
-}
-GradRing& gring() {
-  int dev = 0;
-  hipGetDevice(&dev);
-  aqc::on_finalize(release_gring);
-  return g_gring[dev];
-}
-
-int grad_buffers(GradBuffers& gb, size_t need) {
-  if (gb.pending) {
-    AQC_HIP_CHECK(hipEventSynchronize(gb.done));
-    gb.pending = false;
-  }
-  if (need > gb.cap) {
-    if (gb.dev) hipFree(gb.dev);
-    gb.dev = nullptr;
-    gb.cap = std::max(need, 2 * gb.cap);
-    AQC_HIP_CHECK(hipMalloc(&gb.dev, gb.cap));
-  }
-  if (need > gb.hcap) {
-    if (gb.host) hipHostFree(gb.host);
-    gb.host = nullptr;
-    gb.hcap = std::max(need, 2 * gb.hcap);
-    AQC_HIP_CHECK(hipHostMalloc((void**)&gb.host, gb.hcap, hipHostMallocDefault));
-  }
-  if (!gb.done) AQC_HIP_CHECK(hipEventCreateWithFlags(&gb.done, hipEventDisableTiming));
-  return AQC_OK;
-}
+aqc::PerDevice<GradRing> g_gring;
 
 int ensure_gw(aqc_mps_t h) {
   const size_t cap = h->d.cap, n = h->d.n;
@@ -1010,13 +965,14 @@ int aqc_pair_grads_batch(aqc_mps_t* psis, int ns, const double* svec, const int*
   const size_t o_out = al(o_start + (size_t)n * sizeof(int));
   const size_t image = o_out;  // bytes copied host -> device
   const size_t need = o_out + (out_is_device ? 0 : (size_t)ns * npairs * sizeof(double)) + 256;
-  GradRing& ring = gring();
+  GradRing& ring = g_gring.here();
   std::lock_guard<std::mutex> lk(ring.mu);
-  GradBuffers& gb = ring.b[ring.next];
+  aqc::DevScratch& gb = ring.b[ring.next];
   ring.next ^= 1;
-  rc = grad_buffers(gb, need);
+  rc = gb.wait();
+  if (rc == AQC_OK) rc = gb.ensure(need, need);
   if (rc != AQC_OK) return rc;
-  char* base = (char*)gb.dev;
+  char* base = gb.dev;
   char* hbase = gb.host;
   SweepJob* djobs = (SweepJob*)(base + o_jobs);
   int* dpairs = (int*)(base + o_pairs);
@@ -1109,8 +1065,7 @@ int aqc_pair_grads_batch(aqc_mps_t* psis, int ns, const double* svec, const int*
     hipLaunchKernelGGL(k_sweep_grad, dim3((npairs + 127) / 128, ns), dim3(128), 0, st, djobs, c);
     AQC_CHECK_LAUNCH();
   }
-  AQC_HIP_CHECK(hipEventRecord(gb.done, st));
-  gb.pending = true;
+  if (int e = gb.mark(st)) return e;
   // a host result is complete on return (one wait at the end, none before the launches); a
   // device result is complete on this stream -- the caller joins its own (aqc_stream_join)
   if (!out_is_device && npairs) {
@@ -1204,45 +1159,26 @@ int aqc_argmax_scaled(const double* scores, const double* prio, int count, int s
   AQC_REQUIRE(scores && prio && best && count > 0, "aqc_argmax_scaled: bad arguments");
   hipStream_t st = aqc::mps_stream();
   // cached per-device (pinned host, device) pair: no allocation per call, one copy each way
-  struct ArgmaxBuf {
+  struct Buf : aqc::DevScratch {
     std::mutex mu;
-    double* dev = nullptr;
-    double* host = nullptr;
-    size_t cap = 0;  // doubles
   };
-  static ArgmaxBuf bufs[64];
-  static void (*release)() = [] {
-    for (auto& b : bufs) {
-      if (b.dev) (void)hipFree(b.dev);
-      if (b.host) (void)hipHostFree(b.host);
-      b.dev = nullptr, b.host = nullptr, b.cap = 0;
-    }
-  };
-  aqc::on_finalize(release);
-  int devi = 0;
-  hipGetDevice(&devi);
-  ArgmaxBuf& ab = bufs[devi];
+  static aqc::PerDevice<Buf> bufs;
+  Buf& ab = bufs.here();
   std::lock_guard<std::mutex> lk(ab.mu);
-  const size_t need = 2 * (size_t)count + 4;
-  if (need > ab.cap) {
-    if (ab.dev) hipFree(ab.dev);
-    if (ab.host) hipHostFree(ab.host);
-    ab.dev = nullptr;
-    ab.host = nullptr;
-    ab.cap = std::max(need, 2 * ab.cap);
-    AQC_HIP_CHECK(hipMalloc(&ab.dev, ab.cap * sizeof(double)));
-    AQC_HIP_CHECK(hipHostMalloc((void**)&ab.host, ab.cap * sizeof(double), hipHostMallocDefault));
-  }
-  double* dp = ab.dev;
-  double* ds = ab.dev + count;
-  int* db = (int*)(ab.dev + 2 * (size_t)count);
-  std::memcpy(ab.host, prio, count * sizeof(double));
-  if (!scores_is_device) std::memcpy(ab.host + count, scores, count * sizeof(double));
-  if (int e = aqc::upload_async(dp, ab.host, (scores_is_device ? 1 : 2) * (size_t)count * sizeof(double), st))
+  const size_t need = (2 * (size_t)count + 4) * sizeof(double);
+  if (int rc = ab.ensure(need, need)) return rc;
+  double* dev = (double*)ab.dev;
+  double* host = (double*)ab.host;
+  double* dp = dev;
+  double* ds = dev + count;
+  int* db = (int*)(dev + 2 * (size_t)count);
+  std::memcpy(host, prio, count * sizeof(double));
+  if (!scores_is_device) std::memcpy(host + count, scores, count * sizeof(double));
+  if (int e = aqc::upload_async(dp, host, (scores_is_device ? 1 : 2) * (size_t)count * sizeof(double), st))
     return e;
   hipLaunchKernelGGL(k_argmax, dim3(1), dim3(256), 0, st, scores_is_device ? scores : ds, dp, count, db);
   AQC_CHECK_LAUNCH();
-  int* hb = (int*)(ab.host + 2 * (size_t)count);
+  int* hb = (int*)(host + 2 * (size_t)count);
   AQC_HIP_CHECK(hipMemcpyAsync(hb, db, sizeof(int), hipMemcpyDeviceToHost, st));
   AQC_HIP_CHECK(hipStreamSynchronize(st));
   *best = *hb;

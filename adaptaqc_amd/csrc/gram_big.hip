@@ -1345,6 +1345,7 @@ struct GBBuffers {
   int* host_status = nullptr;
   TwoSiteJob* djobs = nullptr;  // declined jobs for the block Jacobi
   TwoSiteJob* hjobs = nullptr;  // pinned
+  void release();
 };
 
 void gb_free(GBBuffers& b) {
@@ -1356,12 +1357,8 @@ void gb_free(GBBuffers& b) {
   b = GBBuffers();
 }
 
-GBBuffers g_gb_buffers;
-void release_gb_buffers() { gb_free(g_gb_buffers); }
-GBBuffers& gb_buffers() {
-  aqc::on_finalize(release_gb_buffers);
-  return g_gb_buffers;
-}
+void GBBuffers::release() { gb_free(*this); }
+aqc::PerDevice<GBBuffers> g_gb_buffers;
 
 int gb_ensure(GBBuffers& b, int ct, int nj, hipStream_t st) {
   if (b.ct >= ct && b.nj >= nj) return AQC_OK;
@@ -1434,7 +1431,7 @@ hipEvent_t gb_event(int i) {  // (per process; the library stream orders their r
 
 template <int CT>
 int run_gram_big(const TwoSiteJob* hjobs, const TwoSiteJob* jobs, int nj, int cap_max, hipStream_t st) {
-  GBBuffers& b = gb_buffers();
+  GBBuffers& b = g_gb_buffers.here();
   int rc = gb_ensure(b, CT, nj, st);
   if (rc != AQC_OK) return rc;
   GBArgs a;

@@ -2136,97 +2136,42 @@ void schedule(aqc_mps_t h, const aqc_op_t* ops, int nops, bool sort_after, std::
   if (sort_after) s.sort();
 }
 
-// Device staging buffers for job arrays (grown on demand, reused across calls).
-struct Staging {
-  void* dev = nullptr;
-  size_t cap = 0;
-  void* host = nullptr;
-  size_t hcap = 0;
-};
-
-int ensure_staging(Staging& st, size_t bytes) {
-  if (bytes > st.cap) {
-    if (st.dev) hipFree(st.dev);
-    st.cap = std::max(bytes, st.cap * 2);
-    AQC_HIP_CHECK(hipMalloc(&st.dev, st.cap));
-  }
-  if (bytes > st.hcap) {
-    if (st.host) hipHostFree(st.host);
-    st.hcap = std::max(bytes, st.hcap * 2);
-    AQC_HIP_CHECK(hipHostMalloc(&st.host, st.hcap, hipHostMallocDefault));
-  }
-  return AQC_OK;
-}
-
-void free_staging(Staging& s) {
-  if (s.dev) (void)hipFree(s.dev);
-  if (s.host) (void)hipHostFree(s.host);
-  s = Staging();
-}
-Staging g_staging[64];
-void release_staging() {
-  for (auto& s : g_staging) free_staging(s);
-}
-Staging& staging() {
-  int dev = 0;
-  hipGetDevice(&dev);
-  aqc::on_finalize(release_staging);
-  return g_staging[dev];
-}
+// Device and pinned staging for job arrays of the calls that drain the stream first (upload_jobs).
+aqc::PerDevice<aqc::DevScratch> g_staging;
 
 // Job staging for the gate-application launches: a ring of buffer sets per device, each with an
 // event recorded after the launches that read it, so that building the next batch's jobs waits
 // only for the set's previous use (four calls back) instead of draining the stream -- the host
 // schedules while the GPU still runs the previous work.
-struct StagingSet {
-  Staging buf;
-  hipEvent_t done = nullptr;
-  bool pending = false;
+constexpr int kStagingRing = 4;
+struct StagingRing {
+  std::mutex mu;
+  aqc::DevScratch set[kStagingRing];
+  int next = 0;
+  void release() {
+    for (auto& s : set) s.release();
+  }
 };
+aqc::PerDevice<StagingRing> g_stage_rings;
 
 // A lease on the next set of this device's ring.  It holds the device's staging mutex for its
 // lifetime (several host threads may drive one device) and records the set's event on the stream
 // on EVERY exit path -- an early error return included -- so the set is never handed out again
 // while kernels queued before the error may still read it.
-constexpr int kStagingRing = 4;
-StagingSet g_stage_sets[64][kStagingRing];
-void release_stage_sets() {
-  for (auto& dev_sets : g_stage_sets)
-    for (auto& s : dev_sets) {
-      if (s.done) (void)hipEventDestroy(s.done);
-      free_staging(s.buf);
-      s.done = nullptr;
-      s.pending = false;
-    }
-}
 class StagingLease {
  public:
-  explicit StagingLease(hipStream_t st) : st_(st), lk_(mutex_for(device())) {
-    static int next[64] = {0};
-    const int dev = device();
-    aqc::on_finalize(release_stage_sets);
-    ss_ = &g_stage_sets[dev][next[dev]];
-    next[dev] = (next[dev] + 1) % kStagingRing;
-    if (ss_->pending) {
-      const hipError_t e = hipEventSynchronize(ss_->done);
-      if (e != hipSuccess) {
-        aqc::set_error(std::string("staging event wait: ") + hipGetErrorString(e));
-        rc_ = AQC_ERR_HIP;
-      }
-      ss_->pending = false;
-    }
+  explicit StagingLease(hipStream_t st) : st_(st), ring_(g_stage_rings.here()), lk_(ring_.mu) {
+    ss_ = &ring_.set[ring_.next];
+    ring_.next = (ring_.next + 1) % kStagingRing;
+    rc_ = ss_->wait();
   }
   ~StagingLease() {
-    if (!ss_->done && hipEventCreateWithFlags(&ss_->done, hipEventDisableTiming) != hipSuccess) {
-      hipStreamSynchronize(st_);  // no event: drain instead, so the next user finds the set idle
-      return;
-    }
-    if (hipEventRecord(ss_->done, st_) == hipSuccess) ss_->pending = true;
-    else hipStreamSynchronize(st_);
+    // no event: drain instead, so the next user finds the set idle
+    if (ss_->mark(st_) != AQC_OK) hipStreamSynchronize(st_);
   }
   StagingLease(const StagingLease&) = delete;
   StagingLease& operator=(const StagingLease&) = delete;
-  Staging& buf() { return ss_->buf; }
+  aqc::DevScratch& buf() { return *ss_; }
   int rc() const { return rc_; }
 
   // Sizes the leased set for `bytes`.  A set that must grow brings the whole ring to the new size
@@ -2234,34 +2179,21 @@ class StagingLease {
   // calls per step are not a multiple of the ring's length met a fresh (smaller) set in each of
   // its first four steps, and each growth's hipFree drained the device mid-step.
   int ensure(size_t bytes) {
-    Staging& mine = ss_->buf;
-    if (bytes <= mine.cap && bytes <= mine.hcap) return AQC_OK;
-    const size_t want = std::max({bytes, mine.cap * 2, mine.hcap * 2});
-    StagingSet* ring = g_stage_sets[device()];
-    for (int i = 0; i < kStagingRing; ++i) {
-      StagingSet& s = ring[i];
-      if (&s != ss_ && s.pending) {
-        AQC_HIP_CHECK(hipEventSynchronize(s.done));
-        s.pending = false;
-      }
-      if (int rc = ensure_staging(s.buf, want)) return rc;
+    if (bytes <= ss_->cap && bytes <= ss_->hcap) return AQC_OK;
+    const size_t want = std::max({bytes, ss_->cap * 2, ss_->hcap * 2});
+    for (aqc::DevScratch& s : ring_.set) {
+      if (&s != ss_)
+        if (int rc = s.wait()) return rc;
+      if (int rc = s.ensure(want, want)) return rc;
     }
     return AQC_OK;
   }
 
  private:
-  static int device() {
-    int dev = 0;
-    hipGetDevice(&dev);
-    return dev;
-  }
-  static std::mutex& mutex_for(int dev) {
-    static std::mutex m[64];
-    return m[dev];
-  }
   hipStream_t st_;
+  StagingRing& ring_;
   std::unique_lock<std::mutex> lk_;
-  StagingSet* ss_ = nullptr;
+  aqc::DevScratch* ss_ = nullptr;
   int rc_ = AQC_OK;
 };
 
@@ -2380,11 +2312,11 @@ int run_chains(aqc_mps_t* hs, int ns, std::vector<std::vector<DevOp>>& lists, in
   const size_t total = o_chain + (size_t)ns * sizeof(ChainJob);
   StagingLease lease(st);
   if (lease.rc() != AQC_OK) return lease.rc();
-  Staging& sg = lease.buf();
+  aqc::DevScratch& sg = lease.buf();
   int rc = lease.ensure(total);
   if (rc != AQC_OK) return rc;
-  char* hb = (char*)sg.host;
-  char* db = (char*)sg.dev;
+  char* hb = sg.host;
+  char* db = sg.dev;
   TwoSiteJob* h2 = (TwoSiteJob*)(hb + o_two);
   OneSiteJob* h1 = (OneSiteJob*)(hb + o_one);
   int* hcode = (int*)(hb + o_codes);
@@ -2460,11 +2392,6 @@ int run_waves(aqc_mps_t* hs, int ns, std::vector<std::vector<DevOp>>& lists) {
   std::vector<std::pair<size_t, size_t>> two_rng(maxlen), one_rng(maxlen);
   int cap_max = 0;
   for (int s = 0; s < ns; ++s) cap_max = std::max(cap_max, hs[s]->d.cap);
-  // each wave's largest possible theta side (2 chi), from the host bond bounds advanced through
-  // the lists in wave order: 2 chi <= 128 runs the register Jacobi with pivoted-QR
-  // preconditioning (the Gram path in front of it at 2 chi = 128), larger the multi-workgroup
-  // block Jacobi sized by the bound -- so a large-capacity state with small bonds (an unbounded
-  // MPS early in a circuit) does not pay for its capacity
   // Each two-site job's SVD kernel class from its own largest possible theta side (2 chi): the
   // register Jacobi up to 128 (the Gram path in front of it at 128), the block Jacobi sized to the
   // next power of two above (at most 2 cap) -- so a large-capacity state with small bonds does not
@@ -2519,14 +2446,14 @@ int run_waves(aqc_mps_t* hs, int ns, std::vector<std::vector<DevOp>>& lists) {
   const size_t tb = two.size() * sizeof(TwoSiteJob), ob = one.size() * sizeof(OneSiteJob);
   StagingLease lease(st);
   if (lease.rc() != AQC_OK) return lease.rc();
-  Staging& sg = lease.buf();
+  aqc::DevScratch& sg = lease.buf();
   int rc = lease.ensure(tb + ob + 256);
   if (rc != AQC_OK) return rc;
   std::memcpy(sg.host, two.data(), tb);
-  std::memcpy((char*)sg.host + tb, one.data(), ob);
+  std::memcpy(sg.host + tb, one.data(), ob);
   if (int e = aqc::upload_async(sg.dev, sg.host, tb + ob, st)) return e;
   const TwoSiteJob* dtwo = (const TwoSiteJob*)sg.dev;
-  const OneSiteJob* done = (const OneSiteJob*)((char*)sg.dev + tb);
+  const OneSiteJob* done = (const OneSiteJob*)(sg.dev + tb);
   const int tiles = ((cap_max + 15) / 16) * ((cap_max + 15) / 16);
   const int tiles32 = ((cap_max + 31) / 32) * ((cap_max + 31) / 32);
   const int blocks_split = ((2 * cap_max + 63) / 64) * ((2 * cap_max + 63) / 64);
@@ -2612,44 +2539,19 @@ __global__ void k_gather_flags(int* const* __restrict__ flags, int ns, int* __re
 int check_flags_batch(aqc_mps_t* hs, int ns) {
   if (ns <= 0) return AQC_OK;
   if (ns == 1) return check_flags(hs[0]);
-  struct FlagStage {
-    void* dev = nullptr;
-    size_t cap = 0;
-    int* host = nullptr;
-    size_t hcap = 0;
-  };
-  static FlagStage stages[64];
-  static void (*release)() = [] {
-    for (auto& f : stages) {
-      if (f.dev) (void)hipFree(f.dev);
-      if (f.host) (void)hipHostFree(f.host);
-      f = FlagStage();
-    }
-  };
-  aqc::on_finalize(release);
-  int dev = 0;
-  hipGetDevice(&dev);
-  FlagStage& fs = stages[dev];
+  static aqc::PerDevice<aqc::DevScratch> stages;
+  aqc::DevScratch& fs = stages.here();
   const size_t bytes = (size_t)ns * (sizeof(int*) + sizeof(int));
-  if (bytes > fs.cap) {
-    if (fs.dev) hipFree(fs.dev);
-    fs.cap = std::max(bytes, 2 * fs.cap);
-    AQC_HIP_CHECK(hipMalloc(&fs.dev, fs.cap));
-  }
-  if (bytes > fs.hcap) {
-    if (fs.host) hipHostFree(fs.host);
-    fs.hcap = std::max(bytes, 2 * fs.hcap);
-    AQC_HIP_CHECK(hipHostMalloc((void**)&fs.host, fs.hcap, hipHostMallocDefault));
-  }
+  if (int rc = fs.ensure(bytes, bytes)) return rc;
   hipStream_t st = aqc::mps_stream();
   int** hp = (int**)fs.host;
   for (int s = 0; s < ns; ++s) hp[s] = hs[s]->d.flags;
   int** dp = (int**)fs.dev;
-  int* dout = (int*)((char*)fs.dev + (size_t)ns * sizeof(int*));
+  int* dout = (int*)(fs.dev + (size_t)ns * sizeof(int*));
   AQC_HIP_CHECK(hipMemcpyAsync(dp, hp, (size_t)ns * sizeof(int*), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_gather_flags, dim3((ns + 255) / 256), dim3(256), 0, st, (int* const*)dp, ns, dout);
   AQC_CHECK_LAUNCH();
-  int* hout = (int*)((char*)fs.host + (size_t)ns * sizeof(int*));
+  int* hout = (int*)(fs.host + (size_t)ns * sizeof(int*));
   AQC_HIP_CHECK(hipMemcpyAsync(hout, dout, (size_t)ns * sizeof(int), hipMemcpyDeviceToHost, st));
   AQC_HIP_CHECK(hipStreamSynchronize(st));
   int first = AQC_OK;  // every raised flag is read and reset; the first error is reported
@@ -2700,11 +2602,11 @@ MeasJob make_meas(aqc_mps_t h, cplx* out) {
 
 template <typename T>
 int upload_jobs(const std::vector<T>& jobs, const T** dptr) {
-  Staging& sg = staging();
+  aqc::DevScratch& sg = g_staging.here();
   hipStream_t st = aqc::mps_stream();
   AQC_HIP_CHECK(hipStreamSynchronize(st));
   const size_t b = jobs.size() * sizeof(T);
-  int rc = ensure_staging(sg, b + 64);
+  int rc = sg.ensure(b + 64, b + 64);
   if (rc != AQC_OK) return rc;
   std::memcpy(sg.host, jobs.data(), b);
   if (int e = aqc::upload_async(sg.dev, sg.host, b, st)) return e;
@@ -3096,7 +2998,7 @@ int aqc_mps_copy_batch(aqc_mps_t* dst, const aqc_mps_t* src, int ns) {
   hipStream_t st = aqc::mps_stream();
   StagingLease lease(st);  // (the ring: no wait for the stream's earlier work)
   if (lease.rc() != AQC_OK) return lease.rc();
-  Staging& sg = lease.buf();
+  aqc::DevScratch& sg = lease.buf();
   const size_t bytes = jobs.size() * sizeof(CopyJob);
   int rc = lease.ensure(bytes);
   if (rc != AQC_OK) return rc;
@@ -3115,40 +3017,25 @@ int aqc_mps_copy_batch(aqc_mps_t* dst, const aqc_mps_t* src, int ns) {
   return AQC_OK;
 }
 
+// `then` waits for the work queued on `first` so far; an event per device and direction
+static int stream_order(aqc::PerDevice<aqc::DevScratch>& evs, std::mutex& mu, hipStream_t first, hipStream_t then) {
+  std::lock_guard<std::mutex> lk(mu);
+  aqc::DevScratch& e = evs.here();
+  if (int rc = e.mark(first)) return rc;
+  AQC_HIP_CHECK(hipStreamWaitEvent(then, e.done, 0));
+  return AQC_OK;
+}
+
 int aqc_stream_join(void* stream) {
   static std::mutex mu;
-  static hipEvent_t ev[64] = {nullptr};
-  static void (*release)() = [] {
-    for (auto& e : ev)
-      if (e) (void)hipEventDestroy(e), e = nullptr;
-  };
-  aqc::on_finalize(release);
-  int dev = 0;
-  AQC_HIP_CHECK(hipGetDevice(&dev));
-  AQC_REQUIRE(dev >= 0 && dev < 64, "aqc_stream_join: device index out of range");
-  std::lock_guard<std::mutex> lk(mu);
-  if (!ev[dev]) AQC_HIP_CHECK(hipEventCreateWithFlags(&ev[dev], hipEventDisableTiming));
-  AQC_HIP_CHECK(hipEventRecord(ev[dev], aqc::mps_stream()));
-  AQC_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, ev[dev], 0));
-  return AQC_OK;
+  static aqc::PerDevice<aqc::DevScratch> ev;
+  return stream_order(ev, mu, aqc::mps_stream(), (hipStream_t)stream);
 }
 
 int aqc_stream_wait(void* stream) {
   static std::mutex mu;
-  static hipEvent_t ev[64] = {nullptr};
-  static void (*release)() = [] {
-    for (auto& e : ev)
-      if (e) (void)hipEventDestroy(e), e = nullptr;
-  };
-  aqc::on_finalize(release);
-  int dev = 0;
-  AQC_HIP_CHECK(hipGetDevice(&dev));
-  AQC_REQUIRE(dev >= 0 && dev < 64, "aqc_stream_wait: device index out of range");
-  std::lock_guard<std::mutex> lk(mu);
-  if (!ev[dev]) AQC_HIP_CHECK(hipEventCreateWithFlags(&ev[dev], hipEventDisableTiming));
-  AQC_HIP_CHECK(hipEventRecord(ev[dev], (hipStream_t)stream));
-  AQC_HIP_CHECK(hipStreamWaitEvent(aqc::mps_stream(), ev[dev], 0));
-  return AQC_OK;
+  static aqc::PerDevice<aqc::DevScratch> ev;
+  return stream_order(ev, mu, (hipStream_t)stream, aqc::mps_stream());
 }
 
 int aqc_mps_copy(aqc_mps_t dst, const aqc_mps_t src) {
@@ -3242,34 +3129,24 @@ int aqc_mps_overlap_zero_batch(aqc_mps_t* hs, int ns, double* out) {
   if (rc != AQC_OK) return rc;
   // results (ns complex) and the states' gathered error flags (ns ints) in one device buffer: one
   // read-back for both (the caller needs no aqc_mps_check_batch round trip after it)
-  static char* dres[64] = {nullptr};
-  static size_t dres_n[64] = {0};
-  static void (*release)() = [] {
-    for (int d = 0; d < 64; ++d)
-      if (dres[d]) (void)hipFree(dres[d]), dres[d] = nullptr, dres_n[d] = 0;
-  };
-  aqc::on_finalize(release);
-  int dev = 0;
-  hipGetDevice(&dev);
+  static aqc::PerDevice<aqc::DevScratch> dres_tab;
+  aqc::DevScratch& dres = dres_tab.here();
   hipStream_t st = aqc::mps_stream();
   const size_t rbytes = (size_t)ns * sizeof(cplx), need = rbytes + (size_t)ns * sizeof(int);
-  if (dres_n[dev] < need) {
-    AQC_HIP_CHECK(hipStreamSynchronize(st));
-    if (dres[dev]) hipFree(dres[dev]);
-    dres_n[dev] = std::max(need, 2 * dres_n[dev]);
-    AQC_HIP_CHECK(hipMalloc(&dres[dev], dres_n[dev]));
-  }
-  cplx* dr = (cplx*)dres[dev];
-  int* dflags = (int*)(dres[dev] + rbytes);
+  if (dres.cap < need) AQC_HIP_CHECK(hipStreamSynchronize(st));
+  rc = dres.ensure(need);
+  if (rc != AQC_OK) return rc;
+  cplx* dr = (cplx*)dres.dev;
+  int* dflags = (int*)(dres.dev + rbytes);
   // the jobs and flag pointers through a pinned staging set of the ring: no wait for the stream's
   // earlier work (the chain that wrote the states) before these launches are queued
   StagingLease lease(st);
   if (lease.rc() != AQC_OK) return lease.rc();
-  const size_t jb = ((ns * sizeof(MeasJob) + 255) / 256) * 256, fpb = (size_t)ns * sizeof(int*);
+  const size_t jb = aqc::up256(ns * sizeof(MeasJob)), fpb = (size_t)ns * sizeof(int*);
   rc = lease.ensure(jb + fpb);
   if (rc != AQC_OK) return rc;
-  char* hj = (char*)lease.buf().host;
-  char* dj = (char*)lease.buf().dev;
+  char* hj = lease.buf().host;
+  char* dj = lease.buf().dev;
   MeasJob* hjobs = (MeasJob*)hj;
   int** hfp = (int**)(hj + jb);
   for (int s = 0; s < ns; ++s) {
@@ -3288,7 +3165,7 @@ int aqc_mps_overlap_zero_batch(aqc_mps_t* hs, int ns, double* out) {
   hipLaunchKernelGGL(k_gather_flags, dim3((ns + 255) / 256), dim3(256), 0, st, (int* const*)(dj + jb), ns, dflags);
   AQC_CHECK_LAUNCH();
   std::vector<char> hv(need);
-  AQC_HIP_CHECK(hipMemcpyAsync(hv.data(), dres[dev], need, hipMemcpyDeviceToHost, st));
+  AQC_HIP_CHECK(hipMemcpyAsync(hv.data(), dres.dev, need, hipMemcpyDeviceToHost, st));
   AQC_HIP_CHECK(hipStreamSynchronize(st));
   const cplx* v = (const cplx*)hv.data();
   const int* hf = (const int*)(hv.data() + rbytes);
@@ -3323,25 +3200,15 @@ int aqc_mps_amps_hw1_batch(aqc_mps_t* hs, int ns, double* out) {
   for (int s = 0; s < ns; ++s) AQC_REQUIRE(hs[s] && hs[s]->d.n == n, "aqc_mps_amps_hw1_batch: all states need the same n");
   int rc = aqc_mps_sort_batch(hs, ns);
   if (rc != AQC_OK) return rc;
-  static cplx* dres[64] = {nullptr};
-  static size_t dres_n[64] = {0};
-  static void (*release)() = [] {
-    for (int d = 0; d < 64; ++d)
-      if (dres[d]) (void)hipFree(dres[d]), dres[d] = nullptr, dres_n[d] = 0;
-  };
-  aqc::on_finalize(release);
-  int dev = 0;
-  hipGetDevice(&dev);
+  static aqc::PerDevice<aqc::DevScratch> dres_tab;
+  aqc::DevScratch& dres = dres_tab.here();
   hipStream_t st = aqc::mps_stream();
   const size_t need = (size_t)ns * n;
-  if (dres_n[dev] < need) {
-    AQC_HIP_CHECK(hipStreamSynchronize(st));
-    if (dres[dev]) hipFree(dres[dev]);
-    dres_n[dev] = std::max(need, 2 * dres_n[dev]);
-    AQC_HIP_CHECK(hipMalloc(&dres[dev], dres_n[dev] * sizeof(cplx)));
-  }
+  if (dres.cap < need * sizeof(cplx)) AQC_HIP_CHECK(hipStreamSynchronize(st));
+  rc = dres.ensure(need * sizeof(cplx));
+  if (rc != AQC_OK) return rc;
   std::vector<MeasJob> jobs(ns);
-  for (int s = 0; s < ns; ++s) jobs[s] = make_meas(hs[s], dres[dev] + (size_t)s * n);
+  for (int s = 0; s < ns; ++s) jobs[s] = make_meas(hs[s], (cplx*)dres.dev + (size_t)s * n);
   const MeasJob* dj = nullptr;
   rc = upload_jobs(jobs, &dj);
   if (rc != AQC_OK) return rc;
@@ -3351,7 +3218,7 @@ int aqc_mps_amps_hw1_batch(aqc_mps_t* hs, int ns, double* out) {
   AQC_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_hw1, dim3(n, ns), dim3(kT), 0, st, dj);
   AQC_CHECK_LAUNCH();
-  AQC_HIP_CHECK(hipMemcpyAsync(out, dres[dev], need * sizeof(cplx), hipMemcpyDeviceToHost, st));
+  AQC_HIP_CHECK(hipMemcpyAsync(out, dres.dev, need * sizeof(cplx), hipMemcpyDeviceToHost, st));
   AQC_HIP_CHECK(hipStreamSynchronize(st));
   return AQC_OK;
 }
@@ -3423,17 +3290,17 @@ int aqc_mps_zero_hw1_batch(aqc_mps_t base, aqc_mps_t* hs, int ns, double* out_ov
     if (need_l > hl) rows_job(0, hl, need_l - hl, HL);
     if (need_r < hr) rows_job(1, hr - 1, hr - need_r, HR);
     std::vector<HwWinJob> wj;
-    const size_t jb = ((rj.size() * sizeof(HwRowsJob) + 255) / 256) * 256;
-    const size_t wb = ((win.size() * sizeof(HwWinJob) + 255) / 256) * 256;
-    const size_t rb = (((size_t)win.size() * (n + 1) * sizeof(cplx)) + 255) / 256 * 256;
+    const size_t jb = aqc::up256(rj.size() * sizeof(HwRowsJob));
+    const size_t wb = aqc::up256(win.size() * sizeof(HwWinJob));
+    const size_t rb = aqc::up256((size_t)win.size() * (n + 1) * sizeof(cplx));
     const size_t fnb = (size_t)win.size() * 2 * cap * sizeof(cplx);  // the chains' last vectors
-    const size_t cb = ((win.size() * sizeof(int) + 255) / 256) * 256;  // hand-off counters
+    const size_t cb = aqc::up256(win.size() * sizeof(int));  // hand-off counters
     size_t uyb = 0;  // with amps: each state's window vectors (2 (w + 1) cap)
     if (out_amps)
       for (int s : win) uyb += 2 * (size_t)(hi[s] - lo[s] + 2) * cap * sizeof(cplx);
     // the states' and base's error flags are gathered beside the results (one read-back: the
     // caller needs no separate aqc_mps_check_batch round trip)
-    const size_t flb = (((size_t)ns + 1) * sizeof(int) + 255) / 256 * 256;
+    const size_t flb = aqc::up256(((size_t)ns + 1) * sizeof(int));
     char* d = (char*)aqc::dev_alloc(rb + flb + fnb + uyb + 256);
     AQC_REQUIRE(d, "aqc_mps_zero_hw1_batch: out of device memory");
     cplx* res = (cplx*)d;
@@ -3477,8 +3344,8 @@ int aqc_mps_zero_hw1_batch(aqc_mps_t base, aqc_mps_t* hs, int ns, double* out_ov
       aqc::dev_free(d);
       return rc;
     }
-    char* hj = (char*)lease.buf().host;
-    char* dj = (char*)lease.buf().dev;
+    char* hj = lease.buf().host;
+    char* dj = lease.buf().dev;
     for (size_t k = 0; k < wj.size(); ++k) wj[k].cnt = (int*)(dj + jb + wb) + k;
     if (!rj.empty()) std::memcpy(hj, rj.data(), rj.size() * sizeof(HwRowsJob));
     std::memcpy(hj + jb, wj.data(), wj.size() * sizeof(HwWinJob));

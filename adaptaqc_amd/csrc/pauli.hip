@@ -168,35 +168,8 @@ __global__ __launch_bounds__(kThreads) void k_pauli_chain(const PauliJob j) {
 }
 
 // per-device grow-only scratch of the statevector path (masks, partials, results)
-struct Scratch {
-  void* dev = nullptr;
-  size_t cap = 0;
-};
-Scratch g_scr[64];
-void release_scratch() {
-  for (auto& b : g_scr) {
-    if (b.dev) (void)hipFree(b.dev);
-    b = Scratch();
-  }
-}
-int scratch(size_t need, char** out) {
-  int dev = 0;
-  hipGetDevice(&dev);
-  aqc::on_finalize(release_scratch);
-  Scratch& b = g_scr[dev];
-  if (need > b.cap) {
-    if (b.dev) (void)hipFree(b.dev);
-    b.dev = nullptr;
-    b.cap = 0;
-    const size_t want = std::max(need, (size_t)1 << 20);
-    AQC_HIP_CHECK(hipMalloc(&b.dev, want));
-    b.cap = want;
-  }
-  *out = (char*)b.dev;
-  return AQC_OK;
-}
-
-size_t up256(size_t b) { return (b + 255) / 256 * 256; }
+aqc::PerDevice<aqc::DevScratch> g_scr;
+using aqc::up256;
 
 int mps_pauli(aqc_mps_t* hs, int ns, const uint8_t* codes, int nterms, double* out, const char* who) {
   if (!(hs && ns >= 1 && nterms >= 0 && ((codes && out) || nterms == 0))) {
@@ -310,9 +283,10 @@ int aqc_sv_pauli_expect(aqc_sv_t h, const uint64_t* xmask, const uint64_t* zmask
   const int nblk = (int)std::min<uint64_t>(256, std::max<uint64_t>(1, dim / 4096));
   const size_t mb = up256((size_t)nterms * sizeof(uint64_t)), ob = up256((size_t)nterms * sizeof(double));
   const size_t pb = up256((size_t)nterms * nblk * sizeof(double));
-  char* buf = nullptr;
   AQC_HIP_CHECK(hipStreamSynchronize(st));
-  if (int rc = scratch(2 * mb + pb + ob, &buf)) return rc;
+  aqc::DevScratch& sc = g_scr.here();
+  if (int rc = sc.ensure(2 * mb + pb + ob)) return rc;
+  char* buf = sc.dev;
   uint64_t* dx = (uint64_t*)buf;
   uint64_t* dz = (uint64_t*)(buf + mb);
   double* partial = (double*)(buf + 2 * mb);

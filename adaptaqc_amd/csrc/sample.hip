@@ -259,35 +259,8 @@ __global__ __launch_bounds__(kThreads) void k_mps_sample(const SampleJob j) {
 }
 
 // per-device grow-only scratch of the statevector sampler and aqc_sample_uniforms
-struct Scratch {
-  void* dev = nullptr;
-  size_t cap = 0;
-};
-Scratch g_scr[64];
-void release_scratch() {
-  for (auto& b : g_scr) {
-    if (b.dev) (void)hipFree(b.dev);
-    b = Scratch();
-  }
-}
-int scratch(size_t need, char** out) {
-  int dev = 0;
-  hipGetDevice(&dev);
-  aqc::on_finalize(release_scratch);
-  Scratch& b = g_scr[dev];
-  if (need > b.cap) {
-    if (b.dev) (void)hipFree(b.dev);
-    b.dev = nullptr;
-    b.cap = 0;
-    const size_t want = std::max(need, (size_t)1 << 20);
-    AQC_HIP_CHECK(hipMalloc(&b.dev, want));
-    b.cap = want;
-  }
-  *out = (char*)b.dev;
-  return AQC_OK;
-}
-
-size_t up256(size_t b) { return (b + 255) / 256 * 256; }
+aqc::PerDevice<aqc::DevScratch> g_scr;
+using aqc::up256;
 
 int check_uniforms(const double* u, size_t count, const char* who) {
   for (size_t e = 0; e < count; ++e)
@@ -305,9 +278,10 @@ extern "C" {
 int aqc_sample_uniforms(uint64_t seed, uint64_t run, int nshots, int nper, double* out) {
   AQC_REQUIRE(out && nshots >= 1 && nper >= 1, "aqc_sample_uniforms: bad arguments");
   const size_t total = (size_t)nshots * nper;
-  char* buf = nullptr;
   AQC_HIP_CHECK(hipDeviceSynchronize());  // (the scratch may be regrown)
-  if (int rc = scratch(total * sizeof(double), &buf)) return rc;
+  aqc::DevScratch& sc = g_scr.here();
+  if (int rc = sc.ensure(total * sizeof(double))) return rc;
+  char* buf = sc.dev;
   const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, 4096);
   hipLaunchKernelGGL(k_uniforms, dim3(grid), dim3(256), 0, 0, seed, run, nshots, nper, (double*)buf);
   AQC_CHECK_LAUNCH();
@@ -327,9 +301,10 @@ int aqc_sv_sample(aqc_sv_t h, int nshots, uint64_t seed, uint64_t run, const dou
   const uint64_t dim = 1ull << n, ntiles = (dim + kTile - 1) / kTile;
   const size_t sb = up256(ntiles * sizeof(double)), eb = up256((ntiles + 1) * sizeof(double)), mb = 256;
   const size_t ub = up256((size_t)nshots * sizeof(double)), ob = up256((size_t)nshots * sizeof(uint64_t));
-  char* buf = nullptr;
   AQC_HIP_CHECK(hipStreamSynchronize(st));
-  if (int rc = scratch(sb + eb + mb + ub + ob, &buf)) return rc;
+  aqc::DevScratch& sc = g_scr.here();
+  if (int rc = sc.ensure(sb + eb + mb + ub + ob)) return rc;
+  char* buf = sc.dev;
   double* S = (double*)buf;
   double* E = (double*)(buf + sb);
   long long* meta = (long long*)(buf + sb + eb);

@@ -1267,7 +1267,7 @@ int aqc_sv_pair_rdms(aqc_sv_t h, const int* pairs, int npairs, double* out) {
   const size_t per_pair = std::max<size_t>(1, std::min<size_t>(rest / (4 * kThreads), (2048 + npairs - 1) / npairs));
   const int chunks = (int)per_pair;
   char* buf = nullptr;
-  const size_t pb = ((size_t)2 * npairs * sizeof(int) + 255) / 256 * 256;
+  const size_t pb = aqc::up256((size_t)2 * npairs * sizeof(int));
   const size_t qb = (size_t)npairs * chunks * 16 * sizeof(double);
   const size_t ob = (size_t)npairs * 16 * sizeof(cplx);
   int rc = sv_scratch(h, pb + qb + ob, &buf);

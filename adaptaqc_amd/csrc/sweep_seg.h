@@ -132,36 +132,19 @@ __global__ void k_seg_init(cplx* lv0, cplx* rvn, cplx* w, cplx* v0, int cap, siz
 
 // Host plan and launches of the segmented sweep (steps 1-6 above) for one state whose M_i the
 // caller's k_sweep_M has queued; T written for `pairs`; k_sweep_w launched here with `dstart`.
-struct SegScratch {
-  cplx* dev = nullptr;
-  size_t bytes = 0;
-  char* host = nullptr;
-  size_t hbytes = 0;
-  hipEvent_t done = nullptr;
-  bool pending = false;
+struct SegScratch : aqc::DevScratch {
   // the last plan (its job / pointer tables stay on the device): reused while the state's buffers
   // and the pair list are the same -- the per-layer call repeats both
   std::vector<unsigned long long> key;
   std::vector<std::pair<size_t, size_t>> launches;
   std::vector<int> ltiles;
   size_t env_launches = 0, tbl_bytes = 0;
-};
-
-SegScratch g_seg_scratch[64];
-void release_seg_scratch() {
-  for (auto& s : g_seg_scratch) {
-    if (s.done) (void)hipEventDestroy(s.done);
-    if (s.dev) (void)hipFree(s.dev);
-    if (s.host) (void)hipHostFree(s.host);
-    s = SegScratch();
+  void release() {
+    aqc::DevScratch::release();
+    *this = SegScratch();
   }
-}
-SegScratch& seg_scratch() {
-  int dev = 0;
-  hipGetDevice(&dev);
-  aqc::on_finalize(release_seg_scratch);
-  return g_seg_scratch[dev];
-}
+};
+aqc::PerDevice<SegScratch> g_seg_scratch;
 
 int run_segment_sweep(const SweepJob& hj, const SweepJob* djob, const int* pairs, const int* dpairs, int npairs,
                       const int* dstart, hipStream_t st) {
@@ -184,7 +167,7 @@ int run_segment_sweep(const SweepJob& hj, const SweepJob* djob, const int* pairs
   std::vector<CgemmJob> jobs;
   std::vector<std::pair<size_t, size_t>> launches;  // (first job, count)
   std::vector<int> ltiles;
-  SegScratch& sc = seg_scratch();
+  SegScratch& sc = g_seg_scratch.here();
   // (pointers into the device scratch are formed from its base after sizing; plan with offsets)
   const size_t table_off_bytes = oEnd * sizeof(cplx);
   // plan once with a null base to count, then with the real base
@@ -293,28 +276,13 @@ int run_segment_sweep(const SweepJob& hj, const SweepJob* djob, const int* pairs
   const size_t tbl_bytes = reuse ? sc.tbl_bytes : jobs.size() * sizeof(CgemmJob);
   const size_t ptr_bytes = 2 * (size_t)npairs * sizeof(cplx*);
   const size_t need = table_off_bytes + tbl_bytes + ptr_bytes + 256;
-  if (sc.pending && !reuse) {  // the last call's host staging may still be in flight
-    AQC_HIP_CHECK(hipEventSynchronize(sc.done));
-    sc.pending = false;
-  }
-  if (need > sc.bytes) {
-    if (sc.dev) hipFree(sc.dev);
-    sc.dev = nullptr;
-    sc.bytes = 0;
-    sc.key.clear();
-    AQC_HIP_CHECK(hipMalloc(&sc.dev, need));
-    sc.bytes = need;
-  }
-  const size_t hneed = tbl_bytes + ptr_bytes + 256;
-  if (hneed > sc.hbytes) {
-    if (sc.host) hipHostFree(sc.host);
-    sc.host = nullptr;
-    sc.hbytes = 0;
-    AQC_HIP_CHECK(hipHostMalloc((void**)&sc.host, hneed, hipHostMallocDefault));
-    sc.hbytes = hneed;
-  }
-  if (!sc.done) AQC_HIP_CHECK(hipEventCreateWithFlags(&sc.done, hipEventDisableTiming));
-  cplx* base = sc.dev;
+  if (!reuse)  // the last call's host staging may still be in flight
+    if (int rc = sc.wait()) return rc;
+  bool regrown = false;
+  const int erc = sc.ensure(need, tbl_bytes + ptr_bytes + 256, &regrown);
+  if (regrown) sc.key.clear();  // the plan's tables went with the old block
+  if (erc != AQC_OK) return erc;
+  cplx* base = reinterpret_cast<cplx*>(sc.dev);
   char* dtab = reinterpret_cast<char*>(base) + table_off_bytes;
   if (!reuse) {
   env_launches = plan(base);
@@ -372,7 +340,5 @@ int run_segment_sweep(const SweepJob& hj, const SweepJob* djob, const int* pairs
     hipLaunchKernelGGL(k_seg_pairs, dim3((npairs + 3) / 4), dim3(256), 0, st, dx, dy, dpairs, npairs, n, cap, hj.T);
     AQC_CHECK_LAUNCH();
   }
-  AQC_HIP_CHECK(hipEventRecord(sc.done, st));
-  sc.pending = true;
-  return AQC_OK;
+  return sc.mark(st);
 }

@@ -241,35 +241,8 @@ __global__ void k_tomo_fit(const long long* __restrict__ counts, int npairs, cpl
 }
 
 // per-device grow-only scratch
-struct Scratch {
-  void* dev = nullptr;
-  size_t cap = 0;
-};
-Scratch g_scr[64];
-void release_scratch() {
-  for (auto& b : g_scr) {
-    if (b.dev) (void)hipFree(b.dev);
-    b = Scratch();
-  }
-}
-int scratch(size_t need, char** out) {
-  int dev = 0;
-  hipGetDevice(&dev);
-  aqc::on_finalize(release_scratch);
-  Scratch& b = g_scr[dev];
-  if (need > b.cap) {
-    if (b.dev) (void)hipFree(b.dev);
-    b.dev = nullptr;
-    b.cap = 0;
-    const size_t want = std::max(need, (size_t)1 << 20);
-    AQC_HIP_CHECK(hipMalloc(&b.dev, want));
-    b.cap = want;
-  }
-  *out = (char*)b.dev;
-  return AQC_OK;
-}
-
-size_t up256(size_t b) { return (b + 255) / 256 * 256; }
+aqc::PerDevice<aqc::DevScratch> g_scr;
+using aqc::up256;
 
 // does p address device memory?  (plain host memory is unknown to the runtime: an error on some
 // versions, an unregistered type on others)
@@ -290,9 +263,10 @@ int rdm_map(const double* rdms, int npairs, double* out, int on_device, int per,
   const cplx* drdm = (const cplx*)rdms;
   double* dout = out;
   if (!on_device) {
-    char* buf = nullptr;
     AQC_HIP_CHECK(hipStreamSynchronize(st));
-    if (int rc = scratch(rb + ob, &buf)) return rc;
+    aqc::DevScratch& sc = g_scr.here();
+    if (int rc = sc.ensure(rb + ob)) return rc;
+    char* buf = sc.dev;
     AQC_HIP_CHECK(hipMemcpyAsync(buf, rdms, (size_t)npairs * 16 * sizeof(cplx), hipMemcpyHostToDevice, st));
     drdm = (const cplx*)buf;
     dout = (double*)(buf + rb);
@@ -341,9 +315,10 @@ int aqc_multinomial_counts(const double* probs, int njobs, int K, int nshots, ui
   const size_t ub = (u && !udev) ? up256((size_t)nshots * njobs * sizeof(double)) : 0;
   const size_t qb = nchunks > 1 ? up256((size_t)nchunks * total * sizeof(long long)) : 0;
   hipStream_t st = aqc::mps_stream();
-  char* buf = nullptr;
   AQC_HIP_CHECK(hipStreamSynchronize(st));
-  if (int rc = scratch(eb + pb + cb + ub + qb, &buf)) return rc;
+  aqc::DevScratch& sc = g_scr.here();
+  if (int rc = sc.ensure(eb + pb + cb + ub + qb)) return rc;
+  char* buf = sc.dev;
   int* derr = (int*)buf;
   const double* dprobs = pdev ? probs : (const double*)(buf + eb);
   long long* dcounts = cdev ? (long long*)counts : (long long*)(buf + eb + pb);
@@ -384,9 +359,10 @@ int aqc_tomo_fit(const int64_t* counts, int npairs, double* out_rdms, int on_dev
   hipStream_t st = aqc::mps_stream();
   const size_t eb = 256, cb = on_device ? 0 : up256((size_t)npairs * 36 * sizeof(long long));
   const size_t ob = on_device ? 0 : up256((size_t)npairs * 16 * sizeof(cplx));
-  char* buf = nullptr;
   AQC_HIP_CHECK(hipStreamSynchronize(st));
-  if (int rc = scratch(eb + cb + ob, &buf)) return rc;
+  aqc::DevScratch& sc = g_scr.here();
+  if (int rc = sc.ensure(eb + cb + ob)) return rc;
+  char* buf = sc.dev;
   int* derr = (int*)buf;
   const long long* dcounts = on_device ? (const long long*)counts : (const long long*)(buf + eb);
   cplx* dout = on_device ? (cplx*)out_rdms : (cplx*)(buf + eb + cb);

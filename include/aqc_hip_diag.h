@@ -96,6 +96,10 @@ int aqc_debug_hog(int nblocks, double ms);
    for reuse), out[1] bytes handed out, out[2] blocks handed out, out[3] requests served from the
    cache, out[4] requests that went to hipMalloc.  Limit: AQC_POOL_MB (default 8192). */
 int aqc_pool_stats(double* out);
+/* Per-device scratch buffers of the host-side staging (freed by aqc_finalize): out[0] device bytes
+   held, out[1] pinned host bytes held, out[2] device allocations and out[3] pinned allocations
+   made since the library was loaded. */
+int aqc_scratch_stats(double* out);
 /* Batched applies of >= 32 states at 2*chi = 128 run every state's whole op list in
    one fused workgroup (theta, Jacobi, truncation, split per update: no grid-wide step between
    updates); on = 0 selects the lock-step launches per update, on = 2 the fused chain for batches
