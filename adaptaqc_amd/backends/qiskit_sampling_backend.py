@@ -78,8 +78,8 @@ def terminal_measurements(circuit):
 class SamplingSimulator:
     """Stand-in for Aer's ``qasm_simulator`` handle held as ``backend.simulator``.
 
-    ``run(circuit, shots=1024, seed_simulator=None)`` simulates the circuit's gates on the device
-    and draws ``shots`` outcomes of its measurements there; ``result().get_counts()`` gives qiskit's
+    ``run(circuit, shots=1024, seed_simulator=None, noise_model=None)`` simulates the circuit's gates
+    on the device and draws ``shots`` outcomes of its measurements there; ``result().get_counts()`` gives qiskit's
     counts dict (bitstrings over the classical bits, highest leftmost; over all qubits for a circuit
     without measure instructions).  ``method``: "statevector", "matrix_product_state", or
     "automatic" (statevector up to 26 qubits, MPS above).
@@ -94,6 +94,7 @@ class SamplingSimulator:
 
     name = "hip_sampling_simulator"
     METHODS = ("automatic", "statevector", "matrix_product_state")
+    MAX_NOISY_QUBITS = 24  # aqc_sv_traj_sample's limit
 
     def __init__(self, method="automatic", seed=None, mps_truncation_threshold=1e-16, max_chi=None):
         if method not in self.METHODS:
@@ -137,17 +138,40 @@ class SamplingSimulator:
         self._last = (n, method, key, dev)
         return dev
 
-    def run(self, circuit, shots=1024, seed_simulator=None, **ignored):
-        from ..device import counts_from_samples
+    def _noisy_program(self, circuit, noise_model):
+        """(rows, n_events) of the circuit's trajectories under ``noise_model``, or None when no
+        Kraus row comes of it (no model, an empty or all-identity one): the noiseless path then."""
+        from ..noise import trajectory_program
+
+        if noise_model is None:
+            return None
+        rows, n_events, _ = trajectory_program(circuit, noise_model)
+        if n_events == 0:
+            return None
+        n = circuit.num_qubits
+        if self.options.method == "matrix_product_state" or n > self.MAX_NOISY_QUBITS:
+            raise NotImplementedError(
+                "a noise model runs as statevector trajectories only (method 'statevector', or 'automatic' up "
+                f"to {self.MAX_NOISY_QUBITS} qubits): MPS trajectories are not built")
+        return rows, n_events
+
+    def run(self, circuit, shots=1024, seed_simulator=None, noise_model=None, **ignored):
+        """``noise_model`` (adaptaqc_amd.noise.NoiseModel): every shot is then one quantum trajectory on
+        the device (aqc_sv_traj_sample), the errors following the gates they are attached to."""
+        from ..device import counts_from_samples, trajectory_sample
 
         measured = terminal_measurements(circuit)
-        dev = self._state(circuit)
+        noisy = self._noisy_program(circuit, noise_model)
+        dev = self._state(circuit) if noisy is None else None
         if seed_simulator is not None:
             seed, run = int(seed_simulator), 0
         else:
             seed, run = self.seed, self.runs
             self.runs += 1
-        samples = dev.sample(int(shots), seed, run)
+        if noisy is None:
+            samples = dev.sample(int(shots), seed, run)
+        else:
+            samples = trajectory_sample(circuit.num_qubits, noisy[0], noisy[1], int(shots), seed, run)
         counts = counts_from_samples(samples, circuit.num_qubits, measured)
         if measured is not None:  # keys over every classical bit: an unmeasured one reads 0
             width = max(int(getattr(circuit, "num_clbits", 0) or 0), max(measured.values()) + 1)
@@ -238,6 +262,10 @@ class QiskitSamplingBackend(AQCBackend):
     * ``"device"`` (needs a ``SamplingSimulator``): the state is simulated once, the RDMs of all pairs
       are taken on the device, and every setting's counts are drawn from the probabilities the RDM
       fixes (csrc/tomo.hip) -- the law of the counts is that of the nine circuits.
+
+    A ``noise_model`` in the compiler's ``execute_kwargs`` reaches ``SamplingSimulator.run`` with every
+    cost, <Z> and ``"circuits"`` tomography evaluation; ``"device"`` tomography is pure-state and
+    raises when it is given one.
     """
 
     TOMOGRAPHY_MODES = (None, "circuits", "device")
@@ -257,6 +285,11 @@ class QiskitSamplingBackend(AQCBackend):
             raise NotImplementedError("this QiskitSamplingBackend was built without tomography: pass "
                                       "tomography='device' or 'circuits'")
 
+    def _require_noiseless_device_route(self, kwargs):
+        if self.tomography == "device" and kwargs.get("noise_model") is not None:
+            raise NotImplementedError("tomography='device' takes the pairs' RDMs from the pure state and cannot "
+                                      "honour a noise_model: use tomography='circuits'")
+
     def _seed_and_run(self, kwargs):
         """(seed, run) of one device sweep: ``seed_simulator`` alone when given, else the
         simulator's seed and its run counter, which advances once per sweep."""
@@ -274,6 +307,7 @@ class QiskitSamplingBackend(AQCBackend):
 
         self._require_tomography()
         kwargs = dict(execute_kwargs or {})
+        self._require_noiseless_device_route(kwargs)
         pairs = [(int(a), int(b)) for a, b in pairs]
         if self.tomography == "device":
             dev = self.simulator._state(circuit)  # (measures are not part of the cached state's key)
@@ -290,6 +324,7 @@ class QiskitSamplingBackend(AQCBackend):
 
         self._require_tomography()
         kwargs = dict(execute_kwargs or {})
+        self._require_noiseless_device_route(kwargs)
         pairs = [(int(a), int(b)) for a, b in pairs]
         if self.tomography == "device":
             dev = self.simulator._state(circuit)

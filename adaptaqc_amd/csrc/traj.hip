@@ -1,0 +1,417 @@
+// Noisy shot sampling by quantum trajectories: what Aer's qasm_simulator does under a NoiseModel
+// (execute_kwargs={'noise_model': ..., 'shots': ...}, approximate_compiler.py:93).
+//
+// A shot is one trajectory: psi = |0...0>, the program's rows in order, then one draw of all
+// qubits.  A gate row (flags 0) is a 1- or 2-qubit unitary.  A Kraus row (AQC_OP_KRAUS1) holds the
+// 1..4 operators K_k of a one-qubit channel on q0: with p_k = |K_k psi|^2, in-order inclusive sums
+// C_k and P = C_last, event e takes the smallest k with C_k > u_e P (where rounding leaves none, the
+// last k with p_k > 0) and psi <- K_k psi / sqrt(p_k).  The final draw is aqc_sv_sample's rule with
+// u_E.  u_e = sample_uniform(seed, run, shot, e): an outcome depends on (seed, run, shot) only.
+//
+// k_sv_traj: one workgroup carries one trajectory from |0...0> to its outcome and loops over the
+// shots wg, wg + grid, ...; no workgroup waits for another.  Up to 13 qubits the state lives in
+// dynamic LDS (16 * 2^n bytes), beside a staged chunk of program rows (vector loads, as
+// k_sv_segment stages its gates), the chunk's uniforms and a small reduction area; from 14 qubits
+// the same row code runs on the workgroup's slice of a global workspace (slow, but correct).
+//   gate row    the pair / quad pass of k_sv_segment
+//   Kraus row   a reduction pass for the qubit's reduced density matrix (rho00, rho11, rho01:
+//               summed per thread in pair order, over the wave by a butterfly, over the waves in
+//               index order), p_k = Re Tr(K_k^dag K_k rho) with K_k^dag K_k multiplied on the host,
+//               then an apply pass with K_k / sqrt(p_k)
+//   final draw  thread t sums its contiguous amplitudes in order, a wave scan, the wave totals
+//               in order; the first thread whose inclusive sum exceeds u_E P walks its amplitudes
+// No atomics anywhere: two calls return the same bits.
+//
+// LDS layout: interleaved 16-byte complex amplitudes, as k_sv_segment's tile.  Split re / im arrays
+// (8-byte accesses) measured 2-7% slower at 8, 10, 12 and 13 qubits, with equal counts
+// (profiles/trajectory_layout_ab.json), and were removed.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "aqc_internal.h"
+#include "sample_rng.h"
+
+using aqc::cplx;
+
+namespace {
+
+constexpr int kMaxThreads = 512;
+constexpr int kMaxWaves = kMaxThreads / 64;
+constexpr int kChunk = 16;          // program rows staged in LDS at a time (16 x 416 B)
+constexpr int kLdsMaxQubits = 13;   // 2^13 x 16 B = 128 KB of the CU's 160 KB
+constexpr int kMaxQubits = 24;
+constexpr int kMaxShots = 1 << 30;
+constexpr int kMaxGlobalWgs = 256;  // global-workspace path: at most 256 workgroups and 512 MB
+constexpr size_t kMaxGlobalBytes = (size_t)512 << 20;
+
+enum { kGate1 = 0, kGate2 = 1, kKraus = 2 };
+enum { kLds = 0, kGlobal = 1 };
+
+// A program row as the kernel reads it.  Gate: m = the 2x2 / 4x4 matrix.  Kraus: m[8k ..] = K_k,
+// w[4k ..] = (M00, M11, Re M01, Im M01) of M = K_k^dag K_k, ev = the event index.
+struct TrajRow {
+  int32_t kind, q0, q1, nk, ev, pad[3];
+  double m[32];
+  double w[16];
+};
+static_assert(sizeof(TrajRow) == 416 && sizeof(TrajRow) % sizeof(double2) == 0, "TrajRow layout");
+constexpr int kRowWords = (int)(sizeof(TrajRow) / sizeof(double2));
+
+struct TrajJob {
+  const TrajRow* prog;
+  int nprog, n, nshots, nev;
+  const double* u;  // null, or nshots x (nev + 1)
+  uint64_t seed, run;
+  uint64_t* out;
+  uint8_t* choices;  // null, or nshots x nev
+  cplx* ws;          // kGlobal: 2^n amplitudes per workgroup
+};
+
+// bytes of dynamic LDS beside the state
+constexpr size_t kSideBytes = kChunk * sizeof(TrajRow) + kChunk * sizeof(double) + kMaxWaves * 4 * sizeof(double) +
+                              kMaxWaves * sizeof(double) + kMaxWaves * sizeof(int);
+
+template <int MODE>
+struct Amps;
+template <>
+struct Amps<kLds> {
+  cplx* a;
+  __device__ __forceinline__ cplx ld(int i) const { return a[i]; }
+  __device__ __forceinline__ void st(int i, cplx v) const { a[i] = v; }
+};
+template <>
+struct Amps<kGlobal> {
+  cplx* a;
+  __device__ __forceinline__ cplx ld(int i) const { return aqc::ldg(a + i); }
+  __device__ __forceinline__ void st(int i, cplx v) const { aqc::stg(a + i, v); }
+};
+
+__device__ __forceinline__ int insert_zero(int v, int b) { return ((v >> b) << (b + 1)) | (v & ((1 << b) - 1)); }
+
+__device__ __forceinline__ double wave_sum(double v) {
+  for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d, 64);
+  return v;
+}
+__device__ __forceinline__ double wave_scan(double v, int lane) {
+  for (int d = 1; d < 64; d <<= 1) {
+    const double t = __shfl_up(v, d, 64);
+    if (lane >= d) v += t;
+  }
+  return v;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(kMaxThreads) void k_sv_traj(const TrajJob j) {
+  extern __shared__ double2 traj_lds[];
+  const int tid = threadIdx.x, T = blockDim.x, lane = tid & 63, wave = tid >> 6, nwaves = T >> 6;
+  const int n = j.n, dim = 1 << n, half = dim >> 1, quarter = dim >> 2;
+  const int lds_amps = MODE == kGlobal ? 0 : dim;
+  Amps<MODE> psi;
+  if constexpr (MODE == kLds) psi.a = (cplx*)traj_lds;
+  else psi.a = j.ws + (size_t)blockIdx.x * dim;
+  TrajRow* rows = (TrajRow*)(traj_lds + lds_amps);
+  double* ul = (double*)(rows + kChunk);  // the chunk's uniforms
+  double* red = ul + kChunk;              // [wave][4]
+  double* wtot = red + kMaxWaves * 4;     // [wave]
+  int* wlast = (int*)(wtot + kMaxWaves);  // [wave]
+  const int nev = j.nev;
+
+  for (int shot = blockIdx.x; shot < j.nshots; shot += gridDim.x) {
+    for (int i = tid; i < dim; i += T) psi.st(i, aqc::cmk(i == 0 ? 1.0 : 0.0, 0.0));
+    for (int c0 = 0; c0 < j.nprog; c0 += kChunk) {
+      const int nc = min(kChunk, j.nprog - c0);
+      __syncthreads();  // the previous chunk's last row has been applied
+      for (int w = tid; w < nc * kRowWords; w += T)
+        ((double2*)rows)[w] = reinterpret_cast<const double2*>(j.prog + c0)[w];
+      if (tid < nc && j.prog[c0 + tid].kind == kKraus) {
+        const int e = j.prog[c0 + tid].ev;
+        ul[tid] = j.u ? j.u[(size_t)shot * (nev + 1) + e] : aqc::sample_uniform(j.seed, j.run, (uint64_t)shot, (uint32_t)e);
+      }
+      for (int gi = 0; gi < nc; ++gi) {
+        const TrajRow& r = rows[gi];
+        __syncthreads();
+        const int kind = r.kind;
+        if (kind == kGate2) {
+          const int t0 = r.q0, t1 = r.q1;
+          const int lo = t0 < t1 ? t0 : t1, hi = t0 < t1 ? t1 : t0;
+          const cplx* m = (const cplx*)r.m;
+          for (int p = tid; p < quarter; p += T) {
+            const int b = insert_zero(insert_zero(p, lo), hi);
+            int idx[4];
+            cplx v[4];
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+              idx[s] = b | ((s & 1) << t0) | ((s >> 1) << t1);
+              v[s] = psi.ld(idx[s]);
+            }
+#pragma unroll
+            for (int o = 0; o < 4; ++o) {
+              cplx acc = aqc::cmul(m[4 * o], v[0]);
+              acc = aqc::cfma(m[4 * o + 1], v[1], acc);
+              acc = aqc::cfma(m[4 * o + 2], v[2], acc);
+              acc = aqc::cfma(m[4 * o + 3], v[3], acc);
+              psi.st(idx[o], acc);
+            }
+          }
+          continue;
+        }
+        const int t = r.q0;
+        cplx m00, m01, m10, m11;
+        if (kind == kGate1) {
+          const cplx* m = (const cplx*)r.m;
+          m00 = m[0], m01 = m[1], m10 = m[2], m11 = m[3];
+        } else {
+          double r00 = 0.0, r11 = 0.0, rx = 0.0, ry = 0.0;  // rho01 = sum a0 conj(a1)
+          for (int p = tid; p < half; p += T) {
+            const int i0 = insert_zero(p, t);
+            const cplx a0 = psi.ld(i0), a1 = psi.ld(i0 | (1 << t));
+            r00 += aqc::cnorm2(a0);
+            r11 += aqc::cnorm2(a1);
+            const cplx c = aqc::cmulc(a0, a1);
+            rx += c.x;
+            ry += c.y;
+          }
+          r00 = wave_sum(r00);
+          r11 = wave_sum(r11);
+          rx = wave_sum(rx);
+          ry = wave_sum(ry);
+          if (lane == 0) {
+            red[4 * wave] = r00;
+            red[4 * wave + 1] = r11;
+            red[4 * wave + 2] = rx;
+            red[4 * wave + 3] = ry;
+          }
+          __syncthreads();
+          // every thread takes the same sums in the same order, so all choose the same k
+          r00 = r11 = rx = ry = 0.0;
+          for (int w = 0; w < nwaves; ++w) {
+            r00 += red[4 * w];
+            r11 += red[4 * w + 1];
+            rx += red[4 * w + 2];
+            ry += red[4 * w + 3];
+          }
+          const int nk = r.nk;
+          double pk[4], P = 0.0;
+          for (int k = 0; k < 4; ++k) {
+            pk[k] = 0.0;
+            if (k < nk) {
+              const double* w = r.w + 4 * k;
+              pk[k] = fmax(0.0, w[0] * r00 + w[1] * r11 + 2.0 * (w[2] * rx + w[3] * ry));
+              P += pk[k];
+            }
+          }
+          const double target = ul[gi] * P;
+          int k = -1, lastnz = 0;
+          double c = 0.0, psel = 0.0;
+          for (int q = 0; q < 4; ++q) {
+            if (q >= nk) break;
+            c += pk[q];
+            if (pk[q] > 0.0) lastnz = q;
+            if (k < 0 && c > target) k = q;
+          }
+          if (k < 0) k = lastnz;
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            if (q == k) psel = pk[q];
+          const double sc = psel > 0.0 ? 1.0 / sqrt(psel) : 0.0;
+          const cplx* m = (const cplx*)r.m + 4 * k;
+          m00 = aqc::cscale(m[0], sc), m01 = aqc::cscale(m[1], sc);
+          m10 = aqc::cscale(m[2], sc), m11 = aqc::cscale(m[3], sc);
+          if (tid == 0 && j.choices) j.choices[(size_t)shot * nev + r.ev] = (uint8_t)k;
+        }
+        for (int p = tid; p < half; p += T) {
+          const int i0 = insert_zero(p, t), i1 = i0 | (1 << t);
+          const cplx a0 = psi.ld(i0), a1 = psi.ld(i1);
+          psi.st(i0, aqc::cfma(m01, a1, aqc::cmul(m00, a0)));
+          psi.st(i1, aqc::cfma(m11, a1, aqc::cmul(m10, a0)));
+        }
+      }
+    }
+    __syncthreads();
+    // ---- the final draw ----
+    const int cpt = dim >= T ? dim / T : 1;  // contiguous amplitudes per thread
+    const int base = tid * cpt;
+    double s = 0.0;
+    int lastnz = -1;
+    if (base < dim)
+      for (int q = 0; q < cpt; ++q) {
+        const double p = aqc::cnorm2(psi.ld(base + q));
+        if (p > 0.0) lastnz = base + q;
+        s += p;
+      }
+    const double scan = wave_scan(s, lane);
+    int wl = lastnz;
+    for (int d = 1; d < 64; d <<= 1) wl = max(wl, __shfl_xor(wl, d, 64));
+    if (lane == 63) wtot[wave] = scan;
+    if (lane == 0) wlast[wave] = wl;
+    __syncthreads();
+    double off = 0.0, P = 0.0;
+    int last = -1;
+    for (int w = 0; w < nwaves; ++w) {
+      if (w == wave) off = P;
+      P += wtot[w];
+      last = max(last, wlast[w]);
+    }
+    const double uu = j.u ? j.u[(size_t)shot * (nev + 1) + nev]
+                          : aqc::sample_uniform(j.seed, j.run, (uint64_t)shot, (uint32_t)nev);
+    const double target = uu * P;
+    if (!(target < P)) {  // rounding (or the zero vector): the last outcome with p > 0
+      if (tid == 0) j.out[shot] = (uint64_t)(last < 0 ? 0 : last);
+    } else {
+      double prev = __shfl_up(scan, 1, 64);
+      if (lane == 0) prev = 0.0;
+      const double incl = off + scan, excl = off + prev;
+      if (incl > target && !(excl > target)) {  // the first thread whose inclusive sum exceeds the target
+        int idx = -1;
+        double c = excl;
+        for (int q = 0; q < cpt; ++q) {
+          c += aqc::cnorm2(psi.ld(base + q));
+          if (c > target) {
+            idx = base + q;
+            break;
+          }
+        }
+        if (idx < 0) idx = lastnz < 0 ? base : lastnz;
+        j.out[shot] = (uint64_t)idx;
+      }
+    }
+    __syncthreads();  // the draw has read the state before the next shot resets it
+  }
+}
+
+aqc::PerDevice<aqc::DevScratch> g_scr;
+using aqc::up256;
+
+int fail(const std::string& msg) {
+  aqc::set_error("aqc_sv_traj_sample: " + msg);
+  return AQC_ERR_ARG;
+}
+
+// validates the program and writes its device rows; *nev = the number of Kraus rows
+int build_rows(int n, const aqc_op_t* prog, int nprog, std::vector<TrajRow>& rows, int* nev) {
+  rows.assign((size_t)nprog, TrajRow());
+  int ev = 0;
+  for (int i = 0; i < nprog; ++i) {
+    const aqc_op_t& op = prog[i];
+    TrajRow& r = rows[i];
+    std::memset(&r, 0, sizeof(r));
+    if (op.flags == 0) {
+      if (!(op.nq == 1 || op.nq == 2) || op.q0 < 0 || op.q0 >= n) return fail("gate row: bad qubits");
+      if (op.nq == 2 && (op.q1 < 0 || op.q1 >= n || op.q1 == op.q0)) return fail("gate row: bad qubits");
+      r.kind = op.nq == 1 ? kGate1 : kGate2;
+      r.q0 = op.q0;
+      r.q1 = op.nq == 2 ? op.q1 : 0;
+      std::memcpy(r.m, op.m, (op.nq == 1 ? 8 : 32) * sizeof(double));
+    } else if (op.flags == AQC_OP_KRAUS1) {
+      if (op.nq != 1 || op.q0 < 0 || op.q0 >= n || op.q1 < 1 || op.q1 > 4) return fail("malformed Kraus row");
+      r.kind = kKraus;
+      r.q0 = op.q0;
+      r.nk = op.q1;
+      r.ev = ev++;
+      std::memcpy(r.m, op.m, 8 * (size_t)op.q1 * sizeof(double));
+      double s00 = 0.0, s11 = 0.0, sx = 0.0, sy = 0.0;
+      for (int k = 0; k < op.q1; ++k) {
+        const double* K = op.m + 8 * k;  // K00 K01 K10 K11 as (re, im)
+        for (int e = 0; e < 8; ++e)
+          if (!std::isfinite(K[e])) return fail("malformed Kraus row");
+        const double m00 = K[0] * K[0] + K[1] * K[1] + K[4] * K[4] + K[5] * K[5];
+        const double m11 = K[2] * K[2] + K[3] * K[3] + K[6] * K[6] + K[7] * K[7];
+        // M01 = conj(K00) K01 + conj(K10) K11
+        const double mx = K[0] * K[2] + K[1] * K[3] + K[4] * K[6] + K[5] * K[7];
+        const double my = K[0] * K[3] - K[1] * K[2] + K[4] * K[7] - K[5] * K[6];
+        r.w[4 * k] = m00, r.w[4 * k + 1] = m11, r.w[4 * k + 2] = mx, r.w[4 * k + 3] = my;
+        s00 += m00, s11 += m11, sx += mx, sy += my;
+      }
+      if (std::fabs(s00 - 1.0) > 1e-9 || std::fabs(s11 - 1.0) > 1e-9 || std::fabs(sx) > 1e-9 || std::fabs(sy) > 1e-9)
+        return fail("Kraus row: sum K^dag K is not the identity");
+    } else {
+      return fail("unknown row flags");
+    }
+  }
+  *nev = ev;
+  return AQC_OK;
+}
+
+int threads_for(int n) {  // a quarter of the amplitudes, within 64 .. 512
+  const int t = n >= 2 ? 1 << (n - 2) : 1;
+  return std::max(64, std::min(kMaxThreads, t));
+}
+
+template <int MODE>
+int launch(const TrajJob& j, int grid, int threads, size_t dyn) {
+  AQC_HIP_CHECK(hipFuncSetAttribute((const void*)k_sv_traj<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+  hipLaunchKernelGGL(k_sv_traj<MODE>, dim3(grid), dim3(threads), dyn, 0, j);
+  return AQC_OK;
+}
+
+}  // namespace
+
+extern "C" int aqc_sv_traj_sample(int n, const aqc_op_t* prog, int nprog, int nshots, uint64_t seed, uint64_t run,
+                                  const double* u, uint64_t* out, uint8_t* choices) {
+  AQC_REQUIRE(out && nprog >= 0 && (prog || nprog == 0), "aqc_sv_traj_sample: null argument");
+  AQC_REQUIRE(n >= 1 && n <= kMaxQubits, "aqc_sv_traj_sample: n must be in 1 .. 24");
+  AQC_REQUIRE(nshots >= 1 && nshots <= kMaxShots, "aqc_sv_traj_sample: nshots must be in 1 .. 2^30");
+  std::vector<TrajRow> rows;
+  int nev = 0;
+  if (int rc = build_rows(n, prog, nprog, rows, &nev)) return rc;
+  const size_t nu = (size_t)nshots * (nev + 1);
+  if (u)
+    for (size_t e = 0; e < nu; ++e)
+      if (!(u[e] >= 0.0 && u[e] < 1.0)) return fail("u must lie in [0, 1)");
+  const bool want_choices = choices && nev > 0;
+  const size_t dim = (size_t)1 << n;
+  const bool in_lds = n <= kLdsMaxQubits;
+  const int threads = threads_for(n);
+  int grid;
+  if (in_lds) {
+    int dev = 0, cus = 0;
+    AQC_HIP_CHECK(hipGetDevice(&dev));
+    AQC_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    // workgroups that fit a CU together: LDS (160 KB), 32 waves, and at most 8
+    const size_t lds = dim * sizeof(cplx) + kSideBytes;
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>({(size_t)160 * 1024 / lds, (size_t)(2048 / threads), 8}));
+    grid = (int)std::min<size_t>((size_t)nshots, (size_t)std::max(cus, 1) * per_cu);
+  } else {
+    grid = (int)std::max<size_t>(
+        1, std::min<size_t>({(size_t)nshots, (size_t)kMaxGlobalWgs, kMaxGlobalBytes / (dim * sizeof(cplx))}));
+  }
+  const size_t pb = up256(std::max<size_t>(1, rows.size()) * sizeof(TrajRow));
+  const size_t ub = u ? up256(nu * sizeof(double)) : 0;
+  const size_t ob = up256((size_t)nshots * sizeof(uint64_t));
+  const size_t cb = want_choices ? up256((size_t)nshots * nev) : 0;
+  const size_t wb = in_lds ? 0 : (size_t)grid * dim * sizeof(cplx);
+  hipStream_t st = nullptr;
+  AQC_HIP_CHECK(hipDeviceSynchronize());  // (the scratch may be regrown)
+  aqc::DevScratch& sc = g_scr.here();
+  if (int rc = sc.ensure(pb + ub + ob + cb + wb)) return rc;
+  char* buf = sc.dev;
+  TrajJob j;
+  std::memset(&j, 0, sizeof(j));
+  j.prog = (const TrajRow*)buf;
+  j.nprog = nprog;
+  j.n = n;
+  j.nshots = nshots;
+  j.nev = nev;
+  j.u = u ? (const double*)(buf + pb) : nullptr;
+  j.seed = seed;
+  j.run = run;
+  j.out = (uint64_t*)(buf + pb + ub);
+  j.choices = want_choices ? (uint8_t*)(buf + pb + ub + ob) : nullptr;
+  j.ws = in_lds ? nullptr : (cplx*)(buf + pb + ub + ob + cb);
+  if (!rows.empty())
+    AQC_HIP_CHECK(hipMemcpyAsync(buf, rows.data(), rows.size() * sizeof(TrajRow), hipMemcpyHostToDevice, st));
+  if (u) AQC_HIP_CHECK(hipMemcpyAsync(buf + pb, u, nu * sizeof(double), hipMemcpyHostToDevice, st));
+  aqc::KernelTimer::begin(st, "sv_traj", 0.0, (double)nshots * (double)nprog * (double)dim * 14.0);
+  const int rc = in_lds ? launch<kLds>(j, grid, threads, dim * sizeof(cplx) + kSideBytes)
+                        : launch<kGlobal>(j, grid, threads, kSideBytes);
+  aqc::KernelTimer::end(st);
+  if (rc != AQC_OK) return rc;
+  AQC_CHECK_LAUNCH();
+  AQC_HIP_CHECK(hipMemcpyAsync(out, j.out, (size_t)nshots * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  if (want_choices)
+    AQC_HIP_CHECK(hipMemcpyAsync(choices, j.choices, (size_t)nshots * nev, hipMemcpyDeviceToHost, st));
+  AQC_HIP_CHECK(hipStreamSynchronize(st));
+  return AQC_OK;
+}

@@ -275,6 +275,25 @@ def sample_uniforms(seed, run, shots, nper):
     return out
 
 
+def trajectory_sample(n, rows, n_events, shots, seed, run=0, u=None, return_choices=False):
+    """``shots`` noisy shots as quantum trajectories (aqc_sv_traj_sample): uint64[shots] basis indices
+    (bit q = qubit q) of the program ``rows`` (noise.trajectory_program) on n qubits, whose Kraus rows
+    number ``n_events``.  ``u``: [shots, n_events + 1] uniforms in [0, 1) used instead of the
+    generator's (event e in column e, the final draw last).  With ``return_choices`` also the
+    uint8[shots, n_events] Kraus operator chosen at every event."""
+    shots, n_events = int(shots), int(n_events)
+    rows = np.ascontiguousarray(rows, dtype=_lib.OP_DTYPE)
+    if int(np.count_nonzero(rows["flags"] == _lib.OP_KRAUS1)) != n_events:
+        raise ValueError("trajectory_sample: n_events does not match the program's Kraus rows")
+    out = np.zeros(max(shots, 0), dtype=np.uint64)
+    up = _uniforms_arg(u, (shots, n_events + 1))
+    choices = np.zeros((max(shots, 0), n_events), dtype=np.uint8) if return_choices else None
+    _lib.check(_lib.lib().aqc_sv_traj_sample(int(n), _lib.ptr(rows) if len(rows) else None, len(rows), shots, _u64(seed),
+                                             _u64(run), _lib.ptr(up), _lib.ptr(out),
+                                             _lib.ptr(choices) if return_choices and n_events else None))
+    return (out, choices) if return_choices else out
+
+
 def counts_from_samples(samples, n, clbit_of_qubit=None):
     """Counts dict of qiskit bitstrings (highest bit leftmost) from sampler output: uint64[shots]
     basis indices (n <= 64) or uint64[shots, words] packed words.  ``clbit_of_qubit``: {qubit:

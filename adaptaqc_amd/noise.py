@@ -1,0 +1,242 @@
+"""Noise models for the shot backend: one-qubit Kraus channels attached to instruction names, and the
+flat program the device's trajectory sampler runs (csrc/traj.hip, aqc_sv_traj_sample).
+
+Stands in for the parts of ``qiskit_aer.noise`` that the reference uses
+(``execute_kwargs={'noise_model': NoiseModel, 'shots': ...}``, approximate_compiler.py:93;
+``thermal_relaxation_error`` and ``NoiseModel`` in circuit_operations_running.py:72-109).  A noisy
+shot is one quantum trajectory: after every gate that carries an error, one Kraus operator of each
+affected qubit's channel is drawn with probability |K_k psi|^2 and applied.  The law of the counts is
+that of the channel; the individual trajectories depend on the Kraus decomposition chosen here.
+
+Out of scope: correlated two-qubit Kraus sets, readout-error matrices, reset.
+"""
+import numpy as np
+
+_TOL = 1e-9
+_PAULIS = {
+    "I": np.eye(2, dtype=complex),
+    "X": np.array([[0, 1], [1, 0]], dtype=complex),
+    "Y": np.array([[0, -1j], [1j, 0]], dtype=complex),
+    "Z": np.diag([1.0 + 0j, -1.0]),
+}
+
+
+class QuantumError:
+    """A one-qubit channel held as 1-4 Kraus matrices, or a two-qubit product of two such channels
+    (``expand`` / ``tensor``).  ``kraus``: a list of 2x2 complex matrices with sum K^dag K = I
+    within 1e-9."""
+
+    def __init__(self, kraus):
+        mats = [np.array(k, dtype=complex) for k in kraus]
+        if mats and all(m.shape == (4, 4) for m in mats):
+            raise NotImplementedError("correlated two-qubit Kraus errors are not supported: build a product error "
+                                      "with expand() / tensor()")
+        if not 1 <= len(mats) <= 4 or any(m.shape != (2, 2) for m in mats):
+            raise ValueError("QuantumError: 1 to 4 Kraus matrices of shape 2x2")
+        total = sum(m.conj().T @ m for m in mats)
+        if not np.all(np.isfinite(total)) or np.max(np.abs(total - np.eye(2))) > _TOL:
+            raise ValueError("QuantumError: sum K^dag K is not the identity")
+        self.kraus = mats
+        self.pair = None  # (channel of the gate's first listed qubit, of its second)
+        self._identity = all(np.max(np.abs(k - np.trace(k) / 2 * np.eye(2))) <= 1e-12 for k in mats)
+
+    @classmethod
+    def _product(cls, first, second):
+        if first.num_qubits != 1 or second.num_qubits != 1:
+            raise NotImplementedError("only products of two one-qubit errors are supported")
+        e = cls.__new__(cls)
+        e.kraus = None
+        e.pair = (first, second)
+        e._identity = first._identity and second._identity
+        return e
+
+    @property
+    def num_qubits(self):
+        return 1 if self.pair is None else 2
+
+    def expand(self, other):
+        """The two-qubit product error with ``self`` on the gate's first listed qubit."""
+        return QuantumError._product(self, other)
+
+    def tensor(self, other):
+        """The two-qubit product error with ``self`` on the gate's second listed qubit."""
+        return QuantumError._product(other, self)
+
+    def is_identity(self):
+        """True when the channel is the identity map: every Kraus matrix a multiple of I."""
+        return self._identity
+
+    def no_jump_weight(self):
+        """Tr(K_0^dag K_0) / 2 (the product over both qubits for a product error)."""
+        if self.pair is not None:
+            return self.pair[0].no_jump_weight() * self.pair[1].no_jump_weight()
+        return float(np.trace(self.kraus[0].conj().T @ self.kraus[0]).real / 2)
+
+    def __repr__(self):
+        if self.pair is not None:
+            return f"QuantumError(product of {self.pair[0]!r} and {self.pair[1]!r})"
+        return f"QuantumError({len(self.kraus)} Kraus, 1 qubit)"
+
+
+def thermal_relaxation_error(t1, t2, time):
+    """Relaxation towards |0> (excited-state population 0) for ``time``: with gamma = 1 - e^(-time/t1),
+    e2 = e^(-time/t2) and lambda = 1 - gamma - e2^2, K0 = diag(1, e2), K1 = sqrt(gamma) |0><1|,
+    K2 = sqrt(lambda) |1><1|.  The map is rho11 -> e^(-time/t1) rho11, rho01 -> e^(-time/t2) rho01 --
+    Aer's thermal_relaxation_error for every t2 <= 2 t1."""
+    t1, t2, time = float(t1), float(t2), float(time)
+    if not (t1 > 0 and t2 > 0):
+        raise ValueError("thermal_relaxation_error: t1 and t2 must be positive")
+    if not time >= 0:
+        raise ValueError("thermal_relaxation_error: time must not be negative")
+    if t2 > 2 * t1:
+        raise ValueError("thermal_relaxation_error: t2 must not exceed 2 t1")
+    gamma = -np.expm1(-time / t1)
+    e2 = np.exp(-time / t2)
+    lam = max(0.0, 1.0 - gamma - e2 * e2)
+    return QuantumError([np.diag([1.0, e2]), np.sqrt(gamma) * np.array([[0, 1], [0, 0]]),
+                         np.sqrt(lam) * np.diag([0.0, 1.0])])
+
+
+def amplitude_damping_error(gamma):
+    gamma = float(gamma)
+    if not 0 <= gamma <= 1:
+        raise ValueError("amplitude_damping_error: gamma must lie in [0, 1]")
+    return QuantumError([np.diag([1.0, np.sqrt(1 - gamma)]), np.sqrt(gamma) * np.array([[0, 1], [0, 0]])])
+
+
+def phase_damping_error(lam):
+    lam = float(lam)
+    if not 0 <= lam <= 1:
+        raise ValueError("phase_damping_error: lam must lie in [0, 1]")
+    return QuantumError([np.diag([1.0, np.sqrt(1 - lam)]), np.sqrt(lam) * np.diag([0.0, 1.0])])
+
+
+def pauli_error(terms):
+    """[(label, probability), ...] over the one-qubit labels I, X, Y, Z; the probabilities sum to 1."""
+    probs = {}
+    for label, p in terms:
+        if label not in _PAULIS:
+            raise ValueError("pauli_error: one-qubit labels I, X, Y, Z")
+        if not p >= 0:
+            raise ValueError("pauli_error: probabilities must not be negative")
+        probs[label] = probs.get(label, 0.0) + float(p)
+    if not probs or abs(sum(probs.values()) - 1) > _TOL:
+        raise ValueError("pauli_error: probabilities must sum to 1")
+    return QuantumError([np.sqrt(p) * _PAULIS[label] for label, p in probs.items()])
+
+
+def depolarizing_error(p):
+    """rho -> (1 - p) rho + p I / 2 on one qubit (0 <= p <= 4/3), as Aer parametrises it."""
+    p = float(p)
+    if not 0 <= p <= 4 / 3:
+        raise ValueError("depolarizing_error: p must lie in [0, 4/3]")
+    return pauli_error([("I", 1 - 3 * p / 4), ("X", p / 4), ("Y", p / 4), ("Z", p / 4)])
+
+
+def _names(instructions):
+    names = [instructions] if isinstance(instructions, str) else list(instructions)
+    if not names or not all(isinstance(n, str) for n in names):
+        raise ValueError("instructions: a name or a list of names")
+    return names
+
+
+class NoiseModel:
+    """Errors looked up by instruction name (and qubits).  A gate with no error attached is noiseless;
+    a one-qubit error attached to a two-qubit instruction acts on both its qubits."""
+
+    def __init__(self):
+        self._all = {}    # name -> QuantumError
+        self._local = {}  # (name, qubits) -> QuantumError
+
+    def add_all_qubit_quantum_error(self, error, instructions):
+        self._add(self._all, error, _names(instructions))
+
+    def add_quantum_error(self, error, instructions, qubits):
+        qubits = tuple(int(q) for q in qubits)
+        self._add(self._local, error, [(n, qubits) for n in _names(instructions)])
+
+    @staticmethod
+    def _add(table, error, keys):
+        if not isinstance(error, QuantumError):
+            raise TypeError("expected a QuantumError")
+        for key in keys:
+            if key in table:
+                raise NotImplementedError(f"{key} already carries an error: composing errors is not supported")
+            table[key] = error
+
+    def instructions(self):
+        """{name: error} of the all-qubit errors."""
+        return dict(self._all)
+
+    def channels(self, name, qubits):
+        """The one-qubit channels that follow instruction ``name`` on ``qubits``, as [(qubit, error)] in
+        the gate's qubit order (identity channels left out); [] for a noiseless instruction."""
+        qubits = tuple(int(q) for q in qubits)
+        error = self._local.get((name, qubits), self._all.get(name))
+        if error is None:
+            return []
+        if len(qubits) > 2:
+            raise NotImplementedError(f"an error on the {len(qubits)}-qubit gate {name!r} is not supported")
+        if error.num_qubits == 1:
+            per_qubit = [error] * len(qubits)
+        elif len(qubits) == 2:
+            per_qubit = list(error.pair)
+        else:
+            raise ValueError(f"a two-qubit error is attached to the one-qubit instruction {name!r}")
+        return [(q, e) for q, e in zip(qubits, per_qubit) if not e.is_identity()]
+
+    def __repr__(self):
+        return f"NoiseModel(all-qubit: {sorted(self._all)}, local: {sorted(self._local)})"
+
+
+def kraus_row(error, qubit):
+    """One aqc_op_t Kraus row (flags AQC_OP_KRAUS1): q0 the qubit, q1 the number of operators,
+    m[8k .. 8k+7] the k-th 2x2 matrix."""
+    from . import _lib
+
+    row = np.zeros(1, dtype=_lib.OP_DTYPE)
+    row["nq"], row["q0"], row["q1"], row["flags"] = 1, int(qubit), len(error.kraus), _lib.OP_KRAUS1
+    row["m"][0, : 8 * len(error.kraus)] = np.stack(error.kraus).reshape(-1).view(np.float64)
+    return row
+
+
+def trajectory_program(circuit, noise_model):
+    """(rows, n_events, measured): the flat program of aqc_sv_traj_sample for ``circuit`` under
+    ``noise_model``.  Each gate of ``device_ops(circuit)`` is a gate row; after a gate that carries an
+    error one Kraus row follows per affected qubit, in the gate's qubit order; an error attached to
+    "measure" gives one Kraus row per measure instruction, in circuit order, after all gates.
+    Identity channels emit no row.  Event e numbers the Kraus rows in program order.  ``measured``:
+    {qubit: clbit}, or None for a circuit without measures (which must be terminal)."""
+    from . import _lib
+    from .backends.qiskit_sampling_backend import terminal_measurements
+    from .circuit import decompose, qubit_indices
+
+    measured = terminal_measurements(circuit)
+    # the program as a list of slots: a gate piece (matrix, qubits), or a channel (error, qubit);
+    # the gate rows are then converted in one ops_array call and each error's row written once
+    slots, tail = [], []
+    for ins in circuit.data:
+        name = ins.operation.name
+        if name == "set_matrix_product_state":
+            raise ValueError("trajectory_program: a circuit that starts from an MPS cannot run as trajectories")
+        if name in ("barrier", "id", "delay"):
+            continue
+        qs = qubit_indices(circuit, ins)
+        channels = noise_model.channels(name, qs) if noise_model is not None else []
+        if name == "measure":
+            tail += [(e, q) for q, e in channels]
+            continue
+        slots += list(decompose(ins, qs))
+        slots += [(e, q) for q, e in channels]
+    slots += tail
+    is_kraus = np.fromiter((isinstance(s[0], QuantumError) for s in slots), dtype=bool, count=len(slots))
+    rows = np.zeros(len(slots), dtype=_lib.OP_DTYPE)
+    if len(slots) and not is_kraus.all():
+        rows[~is_kraus] = _lib.ops_array([s for s, k in zip(slots, is_kraus) if not k])
+    by_error = {}
+    for i in np.flatnonzero(is_kraus):
+        by_error.setdefault(id(slots[i][0]), []).append(i)
+    for positions in by_error.values():
+        rows[positions] = kraus_row(slots[positions[0]][0], 0)[0]
+    rows["q0"][is_kraus] = [s[1] for s, k in zip(slots, is_kraus) if k]
+    return rows, int(is_kraus.sum()), measured

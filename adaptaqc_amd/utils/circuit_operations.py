@@ -341,6 +341,87 @@ def expectation_value_of_pauli_operator(circuit, operator, backend, backend_opti
     return value
 
 
+# instruction names of this IR by the pulse they stand for, with the reference's times in ns
+# (circuit_operations_running.py:73-79)
+NOISE_INSTRUCTION_TIMES = (
+    (0, ("u1", "p", "rz", "z", "s", "sdg", "t", "tdg")),  # virtual Z
+    (50, ("u2", "h", "sx", "sxdg")),                      # one X90 pulse
+    (100, ("u3", "u", "rx", "ry", "x", "y")),             # two X90 pulses
+    (300, ("cx",)),                                       # on both qubits
+    (1000, ("reset", "measure")),
+)
+
+
+def create_noisemodel(t1, t2, log_fidelities=True):
+    """circuit_operations_running.py:72-109: thermal relaxation after every instruction, with the
+    reference's instruction times (0 / 50 / 100 / 300 / 1000 / 1000 ns for u1 / u2 / u3 / cx / reset /
+    measure) and its scaling of the time constants (t1 and t2 are multiplied by 1e6 and then compared
+    with those times).
+
+    The reference attaches the errors to u1 / u2 / u3 / cx / reset / measure and relies on the
+    transpiler to bring every circuit to those names.  There is no transpiler here, so the errors are
+    also attached to this IR's names for the same pulses (NOISE_INSTRUCTION_TIMES): time 0 (virtual
+    Z) for p, rz, z, s, sdg, t, tdg; 50 ns for h, sx, sxdg; 100 ns for u, rx, ry, x, y.  Any other
+    gate (cz, swap, unitary, ...) stays noiseless, as a gate without an error does in Aer.
+
+    The "fidelity" logged per instruction is the no-jump weight Tr(K_0^dag K_0) / 2."""
+    import logging
+
+    from ..noise import NoiseModel, thermal_relaxation_error
+
+    t1 = t1 * 1e6
+    t2 = t2 * 1e6
+    model = NoiseModel()
+    for time, names in NOISE_INSTRUCTION_TIMES:
+        error = thermal_relaxation_error(t1, t2, time)
+        if names == ("cx",):
+            error = error.expand(thermal_relaxation_error(t1, t2, time))
+        model.add_all_qubit_quantum_error(error, list(names))
+    if log_fidelities:
+        logger = logging.getLogger(__name__)
+        logger.info("Noise model fidelities:")
+        for name, error in model.instructions().items():
+            logger.info(f"['{name}']: {error.no_jump_weight()}")
+    return model
+
+
+def zero_noise_extrapolate(circuit, measurement_function, num_points=10, rng=None):
+    """circuit_operations_running.py:112-139: for each probability in linspace(0, 1, num_points) every
+    cx gets a ``cx cx`` pair inserted in front of it with that probability, ``measurement_function()``
+    is called and ``circuit.data`` is restored; then intercept + amp e^(-x / decay) is fitted to the
+    values and the fit at x = -0.5 is returned.  When the fit fails, ``measurement_function()``.
+    ``rng``: a numpy Generator (default: numpy's global generator, as in the reference)."""
+    import logging
+
+    from scipy.optimize import curve_fit
+
+    draw = rng.random if rng is not None else np.random.random
+    calculated_values = []
+    probabilities = np.linspace(0, 1, num_points)
+    for prob in probabilities:
+        original = circuit.data
+        circuit.data = list(original)
+        try:
+            for i in range(len(original) - 1, -1, -1):
+                ins = original[i]
+                if ins.operation.name == "cx" and draw() < prob:
+                    circuit.data.insert(i, ins)
+                    circuit.data.insert(i, ins)
+            calculated_values.append(measurement_function())
+        finally:
+            circuit.data = original
+
+    def exp_decay(x, intercept, amp, decay_rate):
+        return intercept + amp * np.exp(-1 * x / decay_rate)
+
+    try:
+        popt, _ = curve_fit(exp_decay, probabilities, calculated_values, [0, calculated_values[0], 1])
+        return exp_decay(-0.5, *popt)
+    except RuntimeError as e:
+        logging.getLogger(__name__).warning(f"Failed to zero-noise-extrapolate. Error was {e}")
+        return measurement_function()
+
+
 def calculate_overlap_between_circuits(circuit1, circuit2):
     """|<0|U1^dag U2|0>|^2 = |<psi1|psi2>|^2, evaluated on the device statevector engine."""
     from ..circuit import device_ops

@@ -38,7 +38,7 @@ typedef struct aqc_op {
   int32_t nq;
   int32_t q0;
   int32_t q1;
-  int32_t flags; /* reserved, 0 */
+  int32_t flags; /* 0: a gate; AQC_OP_KRAUS1: a Kraus row of aqc_sv_traj_sample only */
   double m[32];
 } aqc_op_t;
 
@@ -153,6 +153,28 @@ int aqc_sv_sample(aqc_sv_t h, int nshots, uint64_t seed, uint64_t run, const dou
    v = w_bit / sqrt(p_bit).  A pending capacity or SVD flag of queued work: AQC_ERR_STATE, as in
    aqc_mps_overlap_zero. */
 int aqc_mps_sample(aqc_mps_t h, int nshots, uint64_t seed, uint64_t run, const double* u, uint64_t* out);
+
+/* ---- noisy shot sampling: quantum trajectories, replaces Aer's qasm_simulator under a NoiseModel ----
+   (execute_kwargs={'noise_model': ..., 'shots': ...}, approximate_compiler.py:93).
+   prog: nprog rows in order.  flags == 0: a gate, as in aqc_sv_apply.  flags == AQC_OP_KRAUS1: a
+   one-qubit Kraus row on q0 (nq = 1); q1 holds the number of operators (1 .. 4) and m[8k .. 8k+7]
+   the k-th 2x2 matrix.  Event index e numbers the Kraus rows in program order, E = their count.
+   Per shot: psi = |0...0>, then the rows in order.  At Kraus event e: p_k = |K_k psi|^2, C_k the
+   in-order inclusive sums, P = C_last; the smallest k with C_k > u_e P, and where rounding leaves
+   none the last k with p_k > 0 (the statevector sampler's rule); then psi <- K_k psi / sqrt(p_k).
+   After the last row out[shot] = the smallest basis index whose inclusive prefix sum of |psi|^2
+   exceeds u_E total (aqc_sv_sample's rule; the sums run in a fixed order).
+   choices, when not NULL: nshots x E bytes, the chosen k per event.
+   u_e = sample_uniform(seed, run, shot, e) (counter (shot lo, shot hi, e, run)) for e = 0 .. E; when
+   u is not NULL, u_e = u[shot (E+1) + e], host doubles in [0, 1).  An outcome depends on (seed,
+   run, shot) only, not on the grid; no atomics in any reduction: two calls return the same bits.
+   One workgroup carries a trajectory from start to outcome: up to 13 qubits with the state in LDS,
+   from 14 to 24 on a slice of a global workspace (at most 256 workgroups and 512 MB: slow, but correct).
+   AQC_ERR_ARG: n outside 1 .. 24, nshots outside 1 .. 2^30, a u outside [0, 1), a malformed row, or
+   a Kraus row whose sum K^dag K differs from the identity by more than 1e-9. */
+#define AQC_OP_KRAUS1 1
+int aqc_sv_traj_sample(int n, const aqc_op_t* prog, int nprog, int nshots, uint64_t seed, uint64_t run,
+                       const double* u, uint64_t* out, uint8_t* choices);
 
 /* ---- Pauli-string expectation values: replaces circuit_operations_pauli_ops.py:60-100 -------------
    (expectation_value_of_pauli_operator, which runs one rotated circuit per term).
