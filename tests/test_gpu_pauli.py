@@ -8,6 +8,7 @@ import pytest
 import sampling_ref as ref
 from conftest import to_circuit
 from oracle import sv as osv
+from sv_readers_ref import sv_pauli_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -20,25 +21,7 @@ PAULI = {
 }
 
 
-# ---- numpy restatements ------------------------------------------------------------------------
-def sv_pauli_ref(psi, label):
-    """Re sum_k conj(psi[k ^ x]) i^ny (-1)^popcount(k & z) psi[k] with the label's masks."""
-    x = z = ny = 0
-    for q, c in enumerate(reversed(label)):
-        if c in "XY":
-            x |= 1 << q
-        if c in "ZY":
-            z |= 1 << q
-        ny += c == "Y"
-    k = np.arange(len(psi), dtype=np.int64)
-    par = np.zeros(len(psi), dtype=np.int64)
-    kz = k & z
-    while kz.any():
-        par ^= kz & 1
-        kz >>= 1
-    return float(((1j) ** ny * np.sum(np.conj(psi[k ^ x]) * (1 - 2 * par) * psi[k])).real)
-
-
+# ---- numpy restatements (the statevector one is sv_readers_ref.sv_pauli_ref) ---------------------
 def mps_pauli_ref(tensors, label):
     """Transfer-matrix contraction over the whole chain: E <- sum_{s,t} P[s][t] A_s^H E A_t."""
     E = np.ones((1, 1), dtype=complex)
