@@ -220,6 +220,10 @@ struct PerDevice {
   }
 };
 
+// Lets `kernel` be launched with up to `bytes` of dynamic LDS on the current device (the default
+// limit is 64 KB): hipFuncSetAttribute once per device and kernel, again only for a larger limit.
+int allow_dynamic_lds(const void* kernel, int bytes);
+
 // Host -> device copy of a pinned (hipHostMalloc) staging buffer on `st`, done by a kernel that
 // reads the host memory over the bus: the stream's next kernel then depends on a kernel, not on a
 // copy-engine transfer (each of those cost ~10-25 us of idle GPU in the measured timelines,

@@ -664,21 +664,17 @@ int run_block_jacobi(const TwoSiteJob* jobs, int nj, int cap_max, hipStream_t st
 }  // namespace
 
 int block_jacobi(const TwoSiteJob* jobs, int nj, int cap_max, hipStream_t st) {
-  static bool attr = false;
-  if (!attr) {
-    // 128 KB of dynamic LDS (block J's 16 columns of 512 rows)
-    AQC_HIP_CHECK(hipFuncSetAttribute((const void*)k_bj_intra<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072));
-    AQC_HIP_CHECK(hipFuncSetAttribute((const void*)k_bj_intra<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
-    AQC_HIP_CHECK(hipFuncSetAttribute((const void*)k_bj_pair<8, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)kPairLdsBytes));
-    AQC_HIP_CHECK(hipFuncSetAttribute((const void*)k_bj_pair<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)kPairLdsBytes));
-    AQC_HIP_CHECK(hipFuncSetAttribute((const void*)k_bj_pair<16, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)kPairLdsBytes));
-    AQC_HIP_CHECK(hipFuncSetAttribute((const void*)k_bj_pair<32, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)kPairLdsBytes));
-    attr = true;
-  }
+  // 128 KB of dynamic LDS (block J's 16 columns of 512 rows)
+  const std::pair<const void*, int> lds[] = {
+      {(const void*)k_bj_intra<8>, 131072},
+      {(const void*)k_bj_intra<4>, 65536},
+      {(const void*)k_bj_pair<8, false>, (int)kPairLdsBytes},
+      {(const void*)k_bj_pair<4, false>, (int)kPairLdsBytes},
+      {(const void*)k_bj_pair<16, true>, (int)kPairLdsBytes},
+      {(const void*)k_bj_pair<32, true>, (int)kPairLdsBytes},
+  };
+  for (const auto& l : lds)
+    if (int e = allow_dynamic_lds(l.first, l.second)) return e;
   AQC_REQUIRE(2 * cap_max <= 2048, "block Jacobi supports 2 * chi_cap <= 2048");
   if (2 * cap_max <= 256) return run_block_jacobi<4>(jobs, nj, cap_max, st);
   if (2 * cap_max <= 512) return run_block_jacobi<8>(jobs, nj, cap_max, st);

@@ -130,6 +130,24 @@ void DevScratch::release() {
 }
 
 namespace {
+struct RaisedLds {  // kernel -> the limit it was raised to on this device
+  std::map<const void*, int> limit;
+  void release() { limit.clear(); }
+};
+std::mutex g_lds_mutex;
+PerDevice<RaisedLds> g_lds;
+}  // namespace
+
+int allow_dynamic_lds(const void* kernel, int bytes) {
+  std::lock_guard<std::mutex> lk(g_lds_mutex);
+  int& have = g_lds.here().limit[kernel];
+  if (have >= bytes) return AQC_OK;
+  AQC_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  have = bytes;
+  return AQC_OK;
+}
+
+namespace {
 std::mutex g_pool_mutex;
 struct PoolKey {
   int dev;

@@ -1130,11 +1130,9 @@ int aqc_mps_product_fit(aqc_mps_t psi, double* svec, int guess_from_gamma, int m
       break;
     }
     const size_t lds = 5 * (size_t)psi->d.cap * sizeof(cplx);  // (80 KB at capacity 1024)
-    static bool attr = false;
-    if (!attr) {
-      (void)hipFuncSetAttribute((const void*)k_product_fit, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(5 * kFitMaxCap * sizeof(cplx)));
-      attr = true;
+    if (aqc::allow_dynamic_lds((const void*)k_product_fit, (int)(5 * kFitMaxCap * sizeof(cplx))) != AQC_OK) {
+      err = AQC_ERR_HIP;
+      break;
     }
     hipLaunchKernelGGL(k_product_fit, dim3(1), dim3(kT), lds, st, (const FitJob*)dj);
     if (hipGetLastError() != hipSuccess ||

@@ -1,7 +1,9 @@
-// MPS engine internals shared by mps.hip (gate application, measurements) and grad.hip
-// (candidate sweep).
+// MPS engine internals shared by mps.hip (gate application), mps_meas.hip (measurements) and
+// grad.hip (candidate sweep).
 #pragma once
 
+#include <algorithm>
+#include <mutex>
 #include <vector>
 
 #include "aqc_internal.h"
@@ -243,6 +245,89 @@ int big_svd(const TwoSiteJob* hjobs, const TwoSiteJob* jobs, int nj, int side, i
 hipStream_t mps_stream();
 hipStream_t mps_stream_if_any(int dev);
 
+// threadIdx.x read through an empty asm: values a phase derives from it cannot be hoisted out of
+// the chain loop in k_chain (where they would stay live across every other phase)
+__device__ __forceinline__ int fresh_tid() {
+  int t = threadIdx.x;
+  asm volatile("" : "+v"(t));
+  return t;
+}
+
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
+// Job staging for the launches on the MPS stream: a ring of buffer sets per device, each with an
+// event recorded after the launches that read it, so that building the next batch's jobs waits
+// only for the set's previous use (four calls back) instead of draining the stream -- the host
+// schedules while the GPU still runs the previous work.
+constexpr int kStagingRing = 4;
+struct StagingRing {
+  std::mutex mu;
+  DevScratch set[kStagingRing];
+  int next = 0;
+  void release() {
+    for (auto& s : set) s.release();
+  }
+};
+
+StagingRing& staging_ring();  // the current device's (the one table, mps.hip)
+
+// A lease on the next set of this device's ring.  It holds the device's staging mutex for its
+// lifetime (several host threads may drive one device) and records the set's event on the stream
+// on EVERY exit path -- an early error return included -- so the set is never handed out again
+// while kernels queued before the error may still read it.  The mutex is not recursive: no lease is
+// held across a call that takes one (run_waves, and so the sorts, every batched measurement).
+class StagingLease {
+ public:
+  explicit StagingLease(hipStream_t st) : st_(st), ring_(staging_ring()), lk_(ring_.mu) {
+    ss_ = &ring_.set[ring_.next];
+    ring_.next = (ring_.next + 1) % kStagingRing;
+    rc_ = ss_->wait();
+  }
+  ~StagingLease() {
+    // no event: drain instead, so the next user finds the set idle
+    if (ss_->mark(st_) != AQC_OK) hipStreamSynchronize(st_);
+  }
+  StagingLease(const StagingLease&) = delete;
+  StagingLease& operator=(const StagingLease&) = delete;
+  DevScratch& buf() { return *ss_; }
+  int rc() const { return rc_; }
+
+  // Sizes the leased set for `bytes`.  A set that must grow brings the whole ring to the new size
+  // at once (waiting for the other sets' last uses): grown one set at a time, a workload whose
+  // calls per step are not a multiple of the ring's length met a fresh (smaller) set in each of
+  // its first four steps, and each growth's hipFree drained the device mid-step.
+  int ensure(size_t bytes) {
+    if (bytes <= ss_->cap && bytes <= ss_->hcap) return AQC_OK;
+    const size_t want = std::max({bytes, ss_->cap * 2, ss_->hcap * 2});
+    for (DevScratch& s : ring_.set) {
+      if (&s != ss_)
+        if (int rc = s.wait()) return rc;
+      if (int rc = s.ensure(want, want)) return rc;
+    }
+    return AQC_OK;
+  }
+
+ private:
+  hipStream_t st_;
+  StagingRing& ring_;
+  std::unique_lock<std::mutex> lk_;
+  DevScratch* ss_ = nullptr;
+  int rc_ = AQC_OK;
+};
+
+// The error flags of many states in a read-back the caller makes anyway (mps.hip).  The caller puts
+// the states' flag pointers (flag_ptrs) into the staging it uploads, queues the gather of
+// flags[0] | flags[1] per state into `out` (device, ns ints) behind it, and hands the host copy of
+// `out` to settle_flags: every raised flag is read and reset, the first error (in list order) is
+// reported.
+void flag_ptrs(const aqc_mps_t* hs, int ns, int** ptrs);
+int queue_flag_gather(int* const* dptrs, int ns, int* out, hipStream_t st);
+int settle_flags(const aqc_mps_t* hs, int ns, const int* raised);
+
 }  // namespace aqc
 
 // The right environments R_1 .. R_n of one state in sorted qubit order (ent.hip: the chains that
@@ -286,7 +371,7 @@ struct aqc_mps_s {
   // environments up to bond lo and the right ones from bond hi + 1 as they were.
   aqc::cplx* zenv = nullptr;
   int zl = 0, zr = 1 << 30;
-  // Cached zero / Hamming-weight-1 rows (mps.hip, aqc_mps_zero_hw1_batch), per bond b: from the
+  // Cached zero / Hamming-weight-1 rows (mps_meas.hip, aqc_mps_zero_hw1_batch), per bond b: from the
   // left <0..0| A_0 .. A_{b-1} (row 0) and the same with site k < b flipped (row 1 + k); from the
   // right A_b .. A_{n-1} |0..0> (row 0) and with site k >= b flipped (row 1 + k).  Every row is
   // current for bonds <= hl (left) and >= hr (right), row 0 for bonds <= h0l / >= h0r.

@@ -376,7 +376,7 @@ int aqc_mps_sample(aqc_mps_t h, int nshots, uint64_t seed, uint64_t run, const d
   aqc::KernelTimer::begin(st, "mps_sample", 0.0, (double)nshots * n * 8.0 * 4.0 * c2);
   if (vlds) {
     const size_t dyn = (size_t)kShotTile * cap * (sizeof(cplx) + sizeof(double));
-    AQC_HIP_CHECK(hipFuncSetAttribute((const void*)k_mps_sample<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+    if (int e = aqc::allow_dynamic_lds((const void*)k_mps_sample<true>, 96 * 1024)) return e;
     hipLaunchKernelGGL(k_mps_sample<true>, dim3(nwg), dim3(kThreads), dyn, st, j);
   } else {
     hipLaunchKernelGGL(k_mps_sample<false>, dim3(nwg), dim3(kThreads), 0, st, j);

@@ -58,12 +58,6 @@ static_assert(kGramNarrowK == 64, "S5: the narrow inverse iteration (tid < K) st
 // [3] declined at the eigenvalue floor (lambda_K <= 1e-9 lambda_1 -> the Jacobi runs)
 __device__ unsigned long long g_gram_stats[6];  // calls, taken, declined (shape), declined (decision / floor), certificates, certified
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
 // Sum over the 64 lanes, result uniform: DPP row sums, then the four rows through readlane (no
 // LDS crossbar; every lane must be active).
 __device__ __forceinline__ double wave_sum_dpp(double v) {

@@ -341,7 +341,7 @@ int threads_for(int n) {  // a quarter of the amplitudes, within 64 .. 512
 
 template <int MODE>
 int launch(const TrajJob& j, int grid, int threads, size_t dyn) {
-  AQC_HIP_CHECK(hipFuncSetAttribute((const void*)k_sv_traj<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+  if (int e = aqc::allow_dynamic_lds((const void*)k_sv_traj<MODE>, (int)dyn)) return e;
   hipLaunchKernelGGL(k_sv_traj<MODE>, dim3(grid), dim3(threads), dyn, 0, j);
   return AQC_OK;
 }

@@ -4,7 +4,7 @@ sum_i Z_i cached on the prefix (ent.hip k_zenv / k_zsum).  Checked against the f
 (aqc_mps_z_all_batch, itself pinned to the oracle's full contraction) and, for a few states, against
 the oracle directly; the cache is checked as the prefix changes (its pairs stay current only outside
 the rewritten sites).  The same for <psi|0> and <e_i|psi> through a window (aqc_mps_zero_hw1_batch,
-mps.hip k_hw_rows / k_hw_win) against the full chains and the oracle."""
+mps_meas.hip k_hw_rows / k_hw_win) against the full chains and the oracle."""
 
 import numpy as np
 import pytest
