@@ -240,7 +240,8 @@ int upload_async(void* dst, const void* pinned_src, size_t bytes, hipStream_t st
 // still uses.  Each handle's destroy drains its own stream first, and every kernel or copy that
 // reads a handle's buffers on another stream (aqc_sv_copy) makes the owner's stream wait on an
 // event recorded after it, so that drain covers the reader too.  The cache holds at most
-// AQC_POOL_MB (default 8192) MB; an allocation that fails first releases the cache and retries.
+// AQC_POOL_MB (default 8192) MB (a freed block that would exceed it drops cached blocks, the largest
+// sizes first, until it fits); an allocation that fails first releases the cache and retries.
 // aqc_finalize returns every cached block to the runtime.
 void* dev_alloc(size_t bytes);
 void dev_free(void* p);

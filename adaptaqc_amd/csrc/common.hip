@@ -221,6 +221,22 @@ void dev_free(void* p) {
   }
   const PoolKey key = it->second;
   g_pool_live.erase(it);
+  if (g_pool_cached + key.bytes >= g_pool_limit && key.bytes < g_pool_limit) {
+    // The cache is full: drop cached blocks, the largest sizes first, until this one fits.  (Without
+    // this a process that had filled the cache with the blocks of earlier, larger states cached
+    // nothing any more: every later handle of any size paid a hipMalloc and a hipFree.)
+    int cur = 0;
+    const bool have = hipGetDevice(&cur) == hipSuccess;
+    for (auto rit = g_pool_free.rbegin(); rit != g_pool_free.rend() && g_pool_cached + key.bytes >= g_pool_limit; ++rit) {
+      (void)hipSetDevice(rit->first.dev);
+      while (!rit->second.empty() && g_pool_cached + key.bytes >= g_pool_limit) {
+        (void)hipFree(rit->second.back());
+        rit->second.pop_back();
+        g_pool_cached -= rit->first.bytes;
+      }
+    }
+    if (have) (void)hipSetDevice(cur);
+  }
   if (g_pool_cached + key.bytes < g_pool_limit) {
     g_pool_free[key].push_back(p);
     g_pool_cached += key.bytes;
