@@ -18,7 +18,8 @@ OP_DTYPE = np.dtype(
     [("nq", "<i4"), ("q0", "<i4"), ("q1", "<i4"), ("flags", "<i4"), ("m", "<f8", (32,))], align=True
 )
 assert OP_DTYPE.itemsize == 272
-OP_KRAUS1 = 1  # AQC_OP_KRAUS1: a Kraus row of aqc_sv_traj_sample
+OP_KRAUS1 = 1  # AQC_OP_KRAUS1: a Kraus row of aqc_sv_traj_sample / aqc_mps_traj_sample
+OP_MEASURE1 = 2  # AQC_OP_MEASURE1: a measurement row of aqc_mps_traj_plan's schedule
 
 # every symbol declared in include/aqc_hip.h (the drop-in boundary) and include/aqc_hip_diag.h
 # (diagnostics and test hooks)
@@ -43,6 +44,7 @@ EXPORTS = (
     "aqc_scratch_stats",
     "aqc_env_fallbacks", "aqc_env_set_single", "aqc_env_set_spin_limit",
     "aqc_sv_sample", "aqc_mps_sample", "aqc_sample_uniforms", "aqc_sv_traj_sample",
+    "aqc_mps_traj_sample", "aqc_mps_traj_plan", "aqc_mps_traj_set_batch",
     "aqc_sv_pauli_expect", "aqc_mps_pauli_expect", "aqc_mps_pauli_expect_batch",
     "aqc_pair_tomo_probs", "aqc_concurrence_bound_probs", "aqc_multinomial_counts", "aqc_tomo_fit",
 )
@@ -151,6 +153,9 @@ _SIGS = {
     "aqc_mps_sample": ([_P, _I, ctypes.c_uint64, ctypes.c_uint64, _P, _P], _I),
     "aqc_sample_uniforms": ([ctypes.c_uint64, ctypes.c_uint64, _I, _I, _P], _I),
     "aqc_sv_traj_sample": ([_I, _P, _I, _I, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P], _I),
+    "aqc_mps_traj_sample": ([_I, _I, _D, _I, _P, _I, _I, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P], _I),
+    "aqc_mps_traj_plan": ([_I, _P, _I, _P, _P, _I], _I),
+    "aqc_mps_traj_set_batch": ([_I], _I),
     "aqc_sv_pauli_expect": ([_P, _P, _P, _I, _P], _I),
     "aqc_mps_pauli_expect": ([_P, _P, _I, _P], _I),
     "aqc_mps_pauli_expect_batch": ([_P, _I, _P, _I, _P], _I),

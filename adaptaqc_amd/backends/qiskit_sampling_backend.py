@@ -90,19 +90,27 @@ class SamplingSimulator:
 
     With ``seed_simulator`` the shots depend on that seed alone (identical calls give identical
     counts, as with Aer); without it the seed is drawn at construction (or is ``seed``) and every
-    run advances a run counter, so repeated runs are independent."""
+    run advances a run counter, so repeated runs are independent.
+
+    ``mps_trajectories``: a noise model runs as statevector trajectories (at most MAX_NOISY_QUBITS
+    qubits) unless this is True; then method "matrix_product_state", and "automatic" above
+    MAX_NOISY_QUBITS, run it as MPS trajectories (aqc_mps_traj_sample) under the simulator's
+    truncation options.  Opt-in, because an MPS trajectory costs about three two-site SVDs per noisy
+    gate: every Kraus operator has to meet the orthogonality centre."""
 
     name = "hip_sampling_simulator"
     METHODS = ("automatic", "statevector", "matrix_product_state")
     MAX_NOISY_QUBITS = 24  # aqc_sv_traj_sample's limit
 
-    def __init__(self, method="automatic", seed=None, mps_truncation_threshold=1e-16, max_chi=None):
+    def __init__(self, method="automatic", seed=None, mps_truncation_threshold=1e-16, max_chi=None,
+                 mps_trajectories=False):
         if method not in self.METHODS:
             raise ValueError(f"method must be one of {self.METHODS}")
         self.options = SimpleNamespace(method=method, matrix_product_state_truncation_threshold=mps_truncation_threshold,
                                        matrix_product_state_max_bond_dimension=max_chi)
         self.seed = int(seed) if seed is not None else int(np.random.SeedSequence().generate_state(2, np.uint32).view(np.uint64)[0])
         self.runs = 0
+        self.mps_trajectories = bool(mps_trajectories)
         self._last = None  # (n, method, ops bytes, device state)
 
     def __getstate__(self):
@@ -139,7 +147,7 @@ class SamplingSimulator:
         return dev
 
     def _noisy_program(self, circuit, noise_model):
-        """(rows, n_events) of the circuit's trajectories under ``noise_model``, or None when no
+        """(rows, n_events, engine) of the circuit's trajectories under ``noise_model``, or None when no
         Kraus row comes of it (no model, an empty or all-identity one): the noiseless path then."""
         from ..noise import trajectory_program
 
@@ -149,15 +157,43 @@ class SamplingSimulator:
         if n_events == 0:
             return None
         n = circuit.num_qubits
-        if self.options.method == "matrix_product_state" or n > self.MAX_NOISY_QUBITS:
+        method = self.options.method
+        if method == "matrix_product_state" or (method == "automatic" and n > self.MAX_NOISY_QUBITS):
+            if not self.mps_trajectories:
+                raise NotImplementedError(
+                    "a noise model runs as statevector trajectories (method 'statevector', or 'automatic' up to "
+                    f"{self.MAX_NOISY_QUBITS} qubits) unless the simulator is built with mps_trajectories=True, "
+                    "which runs it as MPS trajectories")
+            return rows, n_events, "matrix_product_state"
+        if n > self.MAX_NOISY_QUBITS:
             raise NotImplementedError(
-                "a noise model runs as statevector trajectories only (method 'statevector', or 'automatic' up "
-                f"to {self.MAX_NOISY_QUBITS} qubits): MPS trajectories are not built")
-        return rows, n_events
+                f"statevector trajectories stop at {self.MAX_NOISY_QUBITS} qubits: use method 'automatic' or "
+                "'matrix_product_state' with mps_trajectories=True")
+        return rows, n_events, "statevector"
+
+    def _mps_trajectories(self, n, rows, n_events, shots, seed, run):
+        """The shots as MPS trajectories at the capacity of chi_cap_for; a capacity overflow grows the
+        learned capacity and runs the call again -- the same shots, their uniforms being counters."""
+        from .._lib import AqcError
+        from ..device import mps_trajectory_sample
+        from ..mps_operations import chi_cap_for, grow_capacity, is_capacity_error, learned_capacities
+
+        thr = self.options.matrix_product_state_truncation_threshold
+        max_chi = self.options.matrix_product_state_max_bond_dimension
+        learned = learned_capacities(self)
+        while True:
+            cap = chi_cap_for(n, max_chi, 1, learned)
+            try:
+                return mps_trajectory_sample(n, rows, n_events, shots, seed, run, chi_cap=cap, threshold=thr,
+                                             max_chi=max_chi)
+            except AqcError as e:
+                if not (is_capacity_error(e) and grow_capacity(n, max_chi, cap, learned)):
+                    raise
 
     def run(self, circuit, shots=1024, seed_simulator=None, noise_model=None, **ignored):
         """``noise_model`` (adaptaqc_amd.noise.NoiseModel): every shot is then one quantum trajectory on
-        the device (aqc_sv_traj_sample), the errors following the gates they are attached to."""
+        the device (aqc_sv_traj_sample, or aqc_mps_traj_sample with ``mps_trajectories``), the errors
+        following the gates they are attached to."""
         from ..device import counts_from_samples, trajectory_sample
 
         measured = terminal_measurements(circuit)
@@ -170,8 +206,10 @@ class SamplingSimulator:
             self.runs += 1
         if noisy is None:
             samples = dev.sample(int(shots), seed, run)
-        else:
+        elif noisy[2] == "statevector":
             samples = trajectory_sample(circuit.num_qubits, noisy[0], noisy[1], int(shots), seed, run)
+        else:
+            samples = self._mps_trajectories(circuit.num_qubits, noisy[0], noisy[1], int(shots), seed, run)
         counts = counts_from_samples(samples, circuit.num_qubits, measured)
         if measured is not None:  # keys over every classical bit: an unmeasured one reads 0
             width = max(int(getattr(circuit, "num_clbits", 0) or 0), max(measured.values()) + 1)

@@ -11,7 +11,8 @@
 //     reduce_zeros truncation + renormalisation (k_rank), and the lambda-divided split into the
 //     two new Gammas (k_split_copy, k_split_gemm).
 // Independent states advance in lock-step: one launch of each kernel serves one two-site
-// update of every state in the batch (blockIdx.y / blockIdx.x = job).
+// update of every state in the batch (blockIdx.y / blockIdx.x = job).  The Kraus / measurement rows
+// of noisy trajectories (mps_traj.hip) are a third op kind of the same waves.
 #include <algorithm>
 #include <cmath>
 #include <chrono>
@@ -1363,130 +1364,11 @@ __global__ __launch_bounds__(1024) void k_chain(const ChainJob* __restrict__ cha
 }
 
 // ---- host-side scheduling ---------------------------------------------------------------
-struct DevOp {
-  int kind;  // 1: one-site, 2: two-site (p, p+1)
-  int p;
-  cplx m[16];
-};
-
-inline cplx hc(double r, double i) { return aqc::cmk(r, i); }
-// host complex arithmetic without fma(): the x86 host build has no FMA instructions enabled, so
-// fma() is a libm call per operation
-inline cplx hmul(cplx a, cplx b) { return aqc::cmk(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-inline cplx hfma(cplx a, cplx b, cplx c) { return aqc::cmk(c.x + a.x * b.x - a.y * b.y, c.y + a.x * b.y + a.y * b.x); }
-
-void mat2_mul(const cplx* a, const cplx* b, cplx* out) {  // out = a b (2x2)
-  cplx t[4];
-  for (int r = 0; r < 2; ++r)
-    for (int c = 0; c < 2; ++c)
-      t[r * 2 + c] = hfma(a[r * 2 + 1], b[2 + c], hmul(a[r * 2], b[c]));
-  std::memcpy(out, t, sizeof(t));
-}
-
-struct Scheduler {
-  int n;
-  std::vector<int>& order;
-  std::vector<int>& loc;
-  std::vector<cplx> pend;     // 4 per qubit
-  std::vector<char> has;
-  std::vector<DevOp>& out;
-
-  Scheduler(int n_, std::vector<int>& o, std::vector<int>& l, std::vector<DevOp>& dst)
-      : n(n_), order(o), loc(l), pend(4 * n_), has(n_, 0), out(dst) {}
-
-  void swap_sites(int p) {
-    DevOp d;
-    std::memset(&d, 0, sizeof(d));
-    d.kind = 2;
-    d.p = p;
-    // SWAP in site order: out (s1', s2') = in (s2, s1)
-    for (int o = 0; o < 4; ++o) {
-      const int s1 = o >> 1, s2 = o & 1;
-      const int in = 2 * s2 + s1;
-      d.m[o * 4 + in] = hc(1, 0);
-    }
-    out.push_back(d);
-    const int qa = order[p], qb = order[p + 1];
-    order[p] = qb;
-    order[p + 1] = qa;
-    loc[qa] = p + 1;
-    loc[qb] = p;
-  }
-
-  void one(int q, const double* m) {
-    cplx u[4];
-    for (int e = 0; e < 4; ++e) u[e] = hc(m[2 * e], m[2 * e + 1]);
-    if (!has[q]) {
-      std::memcpy(&pend[4 * q], u, sizeof(u));
-      has[q] = 1;
-    } else {
-      mat2_mul(u, &pend[4 * q], &pend[4 * q]);
-    }
-  }
-
-  void two(int qa, int qb, const double* m) {
-    const int pa = loc[qa], pb = loc[qb];
-    const int low = std::min(pa, pb), high = std::max(pa, pb);
-    for (int i = high; i > low + 1; --i) swap_sites(i - 1);  // change_position(high, low+1)
-    cplx M4[16];
-    for (int e = 0; e < 16; ++e) M4[e] = hc(m[2 * e], m[2 * e + 1]);
-    // fold pending one-qubit gates: M' = M . kron(P_b, P_a)   (index 2*b1 + b0, b0 <-> qa)
-    cplx Pa[4] = {hc(1, 0), hc(0, 0), hc(0, 0), hc(1, 0)}, Pb[4] = {hc(1, 0), hc(0, 0), hc(0, 0), hc(1, 0)};
-    if (has[qa]) std::memcpy(Pa, &pend[4 * qa], sizeof(Pa));
-    if (has[qb]) std::memcpy(Pb, &pend[4 * qb], sizeof(Pb));
-    has[qa] = has[qb] = 0;
-    cplx K[16];
-    for (int r = 0; r < 4; ++r)
-      for (int c = 0; c < 4; ++c) K[r * 4 + c] = hmul(Pb[(r >> 1) * 2 + (c >> 1)], Pa[(r & 1) * 2 + (c & 1)]);
-    cplx Mf[16];
-    for (int r = 0; r < 4; ++r)
-      for (int c = 0; c < 4; ++c) {
-        cplx acc = hc(0, 0);
-        for (int t = 0; t < 4; ++t) acc = hfma(M4[r * 4 + t], K[t * 4 + c], acc);
-        Mf[r * 4 + c] = acc;
-      }
-    // to site order: G[(2 s1' + s2')][(2 s1 + s2)]
-    const bool a_low = loc[qa] == low;
-    DevOp d;
-    std::memset(&d, 0, sizeof(d));
-    d.kind = 2;
-    d.p = low;
-    for (int so = 0; so < 4; ++so)
-      for (int si = 0; si < 4; ++si) {
-        const int s1o = so >> 1, s2o = so & 1, s1i = si >> 1, s2i = si & 1;
-        int ro, ci;
-        if (a_low) {  // b0 = s1 (qa), b1 = s2 (qb)
-          ro = 2 * s2o + s1o;
-          ci = 2 * s2i + s1i;
-        } else {  // b0 = s2 (qa), b1 = s1 (qb)
-          ro = 2 * s1o + s2o;
-          ci = 2 * s1i + s2i;
-        }
-        d.m[so * 4 + si] = Mf[ro * 4 + ci];
-      }
-    out.push_back(d);
-  }
-
-  void flush() {
-    for (int q = 0; q < n; ++q) {
-      if (!has[q]) continue;
-      DevOp d;
-      std::memset(&d, 0, sizeof(d));
-      d.kind = 1;
-      d.p = loc[q];
-      std::memcpy(d.m, &pend[4 * q], 4 * sizeof(cplx));
-      out.push_back(d);
-      has[q] = 0;
-    }
-  }
-
-  void sort() {
-    for (int left = 0; left < n; ++left) {
-      const int pos = loc[left];
-      for (int j = pos; j > left; --j) swap_sites(j - 1);
-    }
-  }
-};
+using aqc::DevOp;
+using aqc::Scheduler;
+using aqc::KrausJob;
+using aqc::TrajCtx;
+using aqc::run_waves;
 
 // Host-side per-state work (scheduling, job building), optionally over a few threads
 // (AQC_HOST_THREADS; f(s) must touch only state s's data).  Default 1: on the MI355X box a batch of
@@ -1700,16 +1582,47 @@ int run_chains(aqc_mps_t* hs, int ns, std::vector<std::vector<DevOp>>& lists, in
   return AQC_OK;  // the lease records the set's event
 }
 
-int run_waves(aqc_mps_t* hs, int ns, std::vector<std::vector<DevOp>>& lists) {
+KrausJob make_kraus(aqc_mps_t h, const DevOp& op, int shot) {
+  KrausJob j;
+  std::memset(&j, 0, sizeof(j));
+  j.g = h->d.site(op.p);
+  j.ll = h->d.bond(op.p);
+  j.lr = h->d.bond(op.p + 1);
+  j.dims = h->d.dims + op.p;
+  j.cap = h->d.cap;
+  j.nk = op.nk;
+  j.slot = op.slot;
+  j.meas = op.meas;
+  j.shot = shot;
+  std::memcpy(j.K, op.m, sizeof(j.K));
+  for (int k = 0; k < op.nk; ++k) {  // M = K_k^dag K_k, as traj.hip's build_rows
+    const cplx* K = op.m + 4 * k;
+    j.w[4 * k] = K[0].x * K[0].x + K[0].y * K[0].y + K[2].x * K[2].x + K[2].y * K[2].y;
+    j.w[4 * k + 1] = K[1].x * K[1].x + K[1].y * K[1].y + K[3].x * K[3].x + K[3].y * K[3].y;
+    j.w[4 * k + 2] = K[0].x * K[1].x + K[0].y * K[1].y + K[2].x * K[3].x + K[2].y * K[3].y;
+    j.w[4 * k + 3] = K[0].x * K[1].y - K[0].y * K[1].x + K[2].x * K[3].y - K[2].y * K[3].x;
+  }
+  return j;
+}
+
+}  // namespace
+
+int aqc::run_waves(aqc_mps_t* hs, int ns, std::vector<std::vector<DevOp>>& lists, const TrajCtx* ctx) {
+  bool kraus = false;
   for (int s = 0; s < ns; ++s) {  // every Gamma these lists write (reload bookkeeping)
     int lo = 1 << 30, hi = -1;
     for (const DevOp& op : lists[s]) {
       lo = std::min(lo, op.p);
       hi = std::max(hi, op.kind == 2 ? op.p + 1 : op.p);
+      kraus |= op.kind == 3;
     }
     if (hi >= 0) hs[s]->changed(lo, hi);
   }
-  {
+  if (kraus && !ctx) {
+    aqc::set_error("run_waves: Kraus rows without a trajectory context");
+    return AQC_ERR_ARG;
+  }
+  if (!kraus) {  // (k_chain has no Kraus phase: such lists run in lock-step whatever the batch)
     int cap_max = 0;
     for (int s = 0; s < ns; ++s) cap_max = std::max(cap_max, hs[s]->d.cap);
     if (g_fused_chain && ns >= g_chain_min_states && 2 * cap_max > 64 && 2 * cap_max <= 128)
@@ -1734,7 +1647,8 @@ int run_waves(aqc_mps_t* hs, int ns, std::vector<std::vector<DevOp>>& lists) {
   // pre-build every wave's jobs into one staging buffer
   std::vector<TwoSiteJob> two;
   std::vector<OneSiteJob> one;
-  std::vector<std::pair<size_t, size_t>> two_rng(maxlen), one_rng(maxlen);
+  std::vector<KrausJob> kr;
+  std::vector<std::pair<size_t, size_t>> two_rng(maxlen), one_rng(maxlen), kr_rng(maxlen);
   int cap_max = 0;
   for (int s = 0; s < ns; ++s) cap_max = std::max(cap_max, hs[s]->d.cap);
   // Each two-site job's SVD kernel class from its own largest possible theta side (2 chi): the
@@ -1759,7 +1673,7 @@ int run_waves(aqc_mps_t* hs, int ns, std::vector<std::vector<DevOp>>& lists) {
   };
   std::vector<std::pair<int, TwoSiteJob>> wjobs;
   for (size_t w = 0; w < maxlen; ++w) {
-    size_t t0 = two.size(), o0 = one.size();
+    size_t t0 = two.size(), o0 = one.size(), k0 = kr.size();
     wjobs.clear();
     for (int s = 0; s < ns; ++s) {
       if (w >= lv[s].size()) continue;
@@ -1774,6 +1688,8 @@ int run_waves(aqc_mps_t* hs, int ns, std::vector<std::vector<DevOp>>& lists) {
           int nb = std::min(2 * std::min(ub[p], ub[p + 2]), hs[s]->d.cap);
           if (hs[s]->max_chi > 0) nb = std::min(nb, hs[s]->max_chi);
           ub[p + 1] = std::max(nb, 1);
+        } else if (op->kind == 3) {
+          kr.push_back(make_kraus(hs[s], *op, ctx->shot0 + s));
         } else {
           one.push_back(make_one(hs[s], *op));
         }
@@ -1787,18 +1703,22 @@ int run_waves(aqc_mps_t* hs, int ns, std::vector<std::vector<DevOp>>& lists) {
     }
     two_rng[w] = {t0, two.size() - t0};
     one_rng[w] = {o0, one.size() - o0};
+    kr_rng[w] = {k0, kr.size() - k0};
   }
-  const size_t tb = two.size() * sizeof(TwoSiteJob), ob = one.size() * sizeof(OneSiteJob);
+  const size_t tb = two.size() * sizeof(TwoSiteJob), ob = aqc::up256(one.size() * sizeof(OneSiteJob));
+  const size_t kb = kr.size() * sizeof(KrausJob);
   StagingLease lease(st);
   if (lease.rc() != AQC_OK) return lease.rc();
   aqc::DevScratch& sg = lease.buf();
-  int rc = lease.ensure(tb + ob + 256);
+  int rc = lease.ensure(tb + ob + kb + 256);
   if (rc != AQC_OK) return rc;
   std::memcpy(sg.host, two.data(), tb);
-  std::memcpy(sg.host + tb, one.data(), ob);
-  if (int e = aqc::upload_async(sg.dev, sg.host, tb + ob, st)) return e;
+  std::memcpy(sg.host + tb, one.data(), one.size() * sizeof(OneSiteJob));
+  if (kb) std::memcpy(sg.host + tb + ob, kr.data(), kb);
+  if (int e = aqc::upload_async(sg.dev, sg.host, kb ? tb + ob + kb : tb + one.size() * sizeof(OneSiteJob), st)) return e;
   const TwoSiteJob* dtwo = (const TwoSiteJob*)sg.dev;
   const OneSiteJob* done = (const OneSiteJob*)(sg.dev + tb);
+  const KrausJob* dkr = (const KrausJob*)(sg.dev + tb + ob);
   const int tiles = ((cap_max + 15) / 16) * ((cap_max + 15) / 16);
   const int tiles32 = ((cap_max + 31) / 32) * ((cap_max + 31) / 32);
   const int blocks_split = ((2 * cap_max + 63) / 64) * ((2 * cap_max + 63) / 64);
@@ -1809,6 +1729,8 @@ int run_waves(aqc_mps_t* hs, int ns, std::vector<std::vector<DevOp>>& lists) {
                          done + one_rng[w].first);
       AQC_CHECK_LAUNCH();
     }
+    if (kr_rng[w].second)
+      if (int e = aqc::launch_kraus(dkr + kr_rng[w].first, (int)kr_rng[w].second, *ctx, st)) return e;
     if (two_rng[w].second) {
       const int nj = (int)two_rng[w].second;
       const TwoSiteJob* jp = dtwo + two_rng[w].first;
@@ -1855,6 +1777,8 @@ int run_waves(aqc_mps_t* hs, int ns, std::vector<std::vector<DevOp>>& lists) {
   return AQC_OK;  // the lease records the set's event
 }
 
+namespace {
+
 int check_flags(aqc_mps_t h) {
   int f[3] = {0, 0, 0};
   AQC_HIP_CHECK(hipMemcpyAsync(f, h->d.flags, sizeof(f), hipMemcpyDeviceToHost, aqc::mps_stream()));
@@ -1877,6 +1801,19 @@ __global__ void k_gather_flags(int* const* __restrict__ flags, int ns, int* __re
 }  // namespace
 
 namespace aqc {
+
+int mps_reset_zero(aqc_mps_s* h) {
+  const int n = h->d.n, cap = h->d.cap;
+  hipStream_t st = mps_stream();
+  AQC_HIP_CHECK(hipMemsetAsync(h->d.gam, 0, (size_t)n * h->d.site_stride() * sizeof(cplx), st));
+  AQC_HIP_CHECK(hipMemsetAsync(h->d.lam, 0, (size_t)(n + 1) * cap * sizeof(double), st));
+  hipLaunchKernelGGL(k_mps_zero, dim3(1 + n / 256), dim3(256), 0, st, h->d.gam, h->d.lam, h->d.dims, n, cap);
+  AQC_CHECK_LAUNCH();
+  for (int i = 0; i < n; ++i) h->order[i] = h->loc[i] = i;
+  h->ub.assign(n + 1, 1);
+  h->changed_all();
+  return AQC_OK;
+}
 
 void flag_ptrs(const aqc_mps_t* hs, int ns, int** ptrs) {
   for (int s = 0; s < ns; ++s) ptrs[s] = hs[s]->d.flags;

@@ -1,5 +1,5 @@
-// MPS engine internals shared by mps.hip (gate application), mps_meas.hip (measurements) and
-// grad.hip (candidate sweep).
+// MPS engine internals shared by mps.hip (gate application), mps_meas.hip (measurements),
+// mps_traj.hip (noisy trajectories) and grad.hip (candidate sweep).
 #pragma once
 
 #include <algorithm>
@@ -318,6 +318,167 @@ class StagingLease {
   DevScratch* ss_ = nullptr;
   int rc_ = AQC_OK;
 };
+
+// ---- host-side scheduling (mps.hip; mps_traj.hip builds its schedules with the same types) --------
+struct DevOp {
+  int kind;  // 1: one-site, 2: two-site (p, p+1), 3: one-site Kraus / measurement row (mps_traj.hip)
+  int p;
+  cplx m[16];  // kind 3: the nk 2x2 operators K_k, 4 elements each
+  // kind 3 only.  nk: the number of operators; slot: the row's uniform and output slot -- the event
+  // index e of a Kraus row, the qubit q of a measurement row (meas = 1, K = {|0><0|, |1><1|})
+  int nk, slot, meas, pad;
+};
+
+// host complex arithmetic without fma(): the x86 host build has no FMA instructions enabled, so
+// fma() is a libm call per operation
+inline cplx hc(double r, double i) { return cmk(r, i); }
+inline cplx hmul(cplx a, cplx b) { return cmk(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+inline cplx hfma(cplx a, cplx b, cplx c) { return cmk(c.x + a.x * b.x - a.y * b.y, c.y + a.x * b.y + a.y * b.x); }
+
+inline void mat2_mul(const cplx* a, const cplx* b, cplx* out) {  // out = a b (2x2)
+  cplx t[4];
+  for (int r = 0; r < 2; ++r)
+    for (int c = 0; c < 2; ++c)
+      t[r * 2 + c] = hfma(a[r * 2 + 1], b[2 + c], hmul(a[r * 2], b[c]));
+  for (int e = 0; e < 4; ++e) out[e] = t[e];
+}
+
+struct Scheduler {
+  int n;
+  std::vector<int>& order;
+  std::vector<int>& loc;
+  std::vector<cplx> pend;     // 4 per qubit
+  std::vector<char> has;
+  std::vector<DevOp>& out;
+
+  Scheduler(int n_, std::vector<int>& o, std::vector<int>& l, std::vector<DevOp>& dst)
+      : n(n_), order(o), loc(l), pend(4 * n_), has(n_, 0), out(dst) {}
+
+  void swap_sites(int p) {
+    DevOp d = DevOp();
+    d.kind = 2;
+    d.p = p;
+    // SWAP in site order: out (s1', s2') = in (s2, s1)
+    for (int o = 0; o < 4; ++o) {
+      const int s1 = o >> 1, s2 = o & 1;
+      const int in = 2 * s2 + s1;
+      d.m[o * 4 + in] = hc(1, 0);
+    }
+    out.push_back(d);
+    const int qa = order[p], qb = order[p + 1];
+    order[p] = qb;
+    order[p + 1] = qa;
+    loc[qa] = p + 1;
+    loc[qb] = p;
+  }
+
+  void one(int q, const double* m) {
+    cplx u[4];
+    for (int e = 0; e < 4; ++e) u[e] = hc(m[2 * e], m[2 * e + 1]);
+    if (!has[q]) {
+      for (int e = 0; e < 4; ++e) pend[4 * q + e] = u[e];
+      has[q] = 1;
+    } else {
+      mat2_mul(u, &pend[4 * q], &pend[4 * q]);
+    }
+  }
+
+  void two(int qa, int qb, const double* m) {
+    const int pa = loc[qa], pb = loc[qb];
+    const int low = std::min(pa, pb), high = std::max(pa, pb);
+    for (int i = high; i > low + 1; --i) swap_sites(i - 1);  // change_position(high, low+1)
+    cplx M4[16];
+    for (int e = 0; e < 16; ++e) M4[e] = hc(m[2 * e], m[2 * e + 1]);
+    // fold pending one-qubit gates: M' = M . kron(P_b, P_a)   (index 2*b1 + b0, b0 <-> qa)
+    cplx Pa[4] = {hc(1, 0), hc(0, 0), hc(0, 0), hc(1, 0)}, Pb[4] = {hc(1, 0), hc(0, 0), hc(0, 0), hc(1, 0)};
+    if (has[qa])
+      for (int e = 0; e < 4; ++e) Pa[e] = pend[4 * qa + e];
+    if (has[qb])
+      for (int e = 0; e < 4; ++e) Pb[e] = pend[4 * qb + e];
+    has[qa] = has[qb] = 0;
+    cplx K[16];
+    for (int r = 0; r < 4; ++r)
+      for (int c = 0; c < 4; ++c) K[r * 4 + c] = hmul(Pb[(r >> 1) * 2 + (c >> 1)], Pa[(r & 1) * 2 + (c & 1)]);
+    cplx Mf[16];
+    for (int r = 0; r < 4; ++r)
+      for (int c = 0; c < 4; ++c) {
+        cplx acc = hc(0, 0);
+        for (int t = 0; t < 4; ++t) acc = hfma(M4[r * 4 + t], K[t * 4 + c], acc);
+        Mf[r * 4 + c] = acc;
+      }
+    // to site order: G[(2 s1' + s2')][(2 s1 + s2)]
+    const bool a_low = loc[qa] == low;
+    DevOp d = DevOp();
+    d.kind = 2;
+    d.p = low;
+    for (int so = 0; so < 4; ++so)
+      for (int si = 0; si < 4; ++si) {
+        const int s1o = so >> 1, s2o = so & 1, s1i = si >> 1, s2i = si & 1;
+        int ro, ci;
+        if (a_low) {  // b0 = s1 (qa), b1 = s2 (qb)
+          ro = 2 * s2o + s1o;
+          ci = 2 * s2i + s1i;
+        } else {  // b0 = s2 (qa), b1 = s1 (qb)
+          ro = 2 * s1o + s2o;
+          ci = 2 * s1i + s2i;
+        }
+        d.m[so * 4 + si] = Mf[ro * 4 + ci];
+      }
+    out.push_back(d);
+  }
+
+  void flush() {
+    for (int q = 0; q < n; ++q) {
+      if (!has[q]) continue;
+      DevOp d = DevOp();
+      d.kind = 1;
+      d.p = loc[q];
+      for (int e = 0; e < 4; ++e) d.m[e] = pend[4 * q + e];
+      out.push_back(d);
+      has[q] = 0;
+    }
+  }
+
+  void sort() {
+    for (int left = 0; left < n; ++left) {
+      const int pos = loc[left];
+      for (int j = pos; j > left; --j) swap_sites(j - 1);
+    }
+  }
+};
+
+// What the Kraus / measurement rows of a batch of trajectories share (mps_traj.hip): state s of the
+// lists handed to run_waves carries shot shot0 + s.  Row slots: Kraus event e -> e, the measurement of
+// qubit q -> nev + q, out of nper = nev + n per shot.
+struct TrajCtx {
+  uint64_t seed, run;
+  const double* u;   // device: null, or [shot][nper] uniforms replacing sample_uniform(seed, run, shot, slot)
+  uint64_t* out;     // device: [shot][words] outcome words, zeroed by the caller
+  uint8_t* choices;  // device: null, or [shot][nev]
+  int shot0, nev, nper, words;
+};
+
+// One Kraus / measurement row of one state, as k_mps_kraus1 reads it (mps_traj.hip).
+struct KrausJob {
+  cplx* g;           // the site's Gamma [2][cap][cap]
+  const double* ll;  // lambda left of the site
+  const double* lr;  // lambda right of it
+  const int* dims;   // &dims[p]
+  int cap, nk, slot, meas;
+  int shot, pad;
+  cplx K[16];        // K_k at K + 4 k
+  double w[16];      // (M00, M11, Re M01, Im M01) of M = K_k^dag K_k at w + 4 k
+};
+
+// Queues k_mps_kraus1 over nj device jobs on st (mps_traj.hip).
+int launch_kraus(const KrausJob* jobs, int nj, const TrajCtx& ctx, hipStream_t st);
+
+// Runs per-state device-op lists in lock-step waves on the MPS stream (mps.hip); returns once the
+// work is queued.  Lists with kind-3 rows need ctx and never take the fused chain.
+int run_waves(aqc_mps_s** hs, int ns, std::vector<std::vector<DevOp>>& lists, const TrajCtx* ctx = nullptr);
+
+// The handle back to |0...0> in sorted qubit order, queued on the MPS stream (mps.hip).
+int mps_reset_zero(aqc_mps_s* h);
 
 // The error flags of many states in a read-back the caller makes anyway (mps.hip).  The caller puts
 // the states' flag pointers (flag_ptrs) into the staging it uploads, queues the gather of

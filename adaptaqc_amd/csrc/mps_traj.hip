@@ -1,0 +1,448 @@
+// Noisy shot sampling on the MPS engine: quantum trajectories above the statevector's 24 qubits, what
+// Aer's qasm_simulator does with method="matrix_product_state" under a NoiseModel.
+//
+// A shot is one trajectory of aqc_sv_traj_sample's program (traj.hip) on a Vidal MPS: the gate rows
+// run as the engine's two-site updates (swap-left routing, run_waves in mps.hip), a Kraus row draws
+// one operator of a one-qubit channel and applies it to the site, and the final measurement draws
+// the qubits one by one.  A Kraus operator is not unitary, so it breaks the canonical form at every
+// bond, and the one-site formula for the qubit's reduced density matrix,
+//   rho[s][s'] = sum_{l,r} lambda_p[l]^2 lambda_{p+1}[r]^2 Gamma_p^s[l][r] conj(Gamma_p^s'[l][r]),
+// holds only at the orthogonality centre.  The schedule therefore tracks the centre on the host, by
+// two integers that depend on the program alone: every site < a is left-orthonormal (sum_s (lambda_j
+// Gamma_j^s)^H (lambda_j Gamma_j^s) = I), every site > b right-orthonormal (sum_s (Gamma_j^s
+// lambda_{j+1}) (Gamma_j^s lambda_{j+1})^H = I); canonical: a = n, b = -1.
+//   two-site update on (p, p+1)   needs a >= p and b <= p+1 (theta's environments are identities, so
+//                                 the SVD is the Schmidt decomposition and the truncation Aer's);
+//                                 then a = a >= p+2 ? a : p+1 and b = b <= p-1 ? b : p
+//   Kraus / measurement row on p  needs a >= p and b <= p; then a = b = p
+//   centre moves                  identity-gate two-site updates: on (a, a+1) while a < p, on
+//                                 (b-1, b) while b > the row's right site (b <= a always, so both
+//                                 are legal)
+// One-qubit unitaries keep both properties and stay deferred; a Kraus row on a qubit with a pending
+// gate P absorbs it (K_k <- K_k P).  The final measurement: flush, sort, then for q = 0 .. n-1 a
+// measurement row {|0><0|, |1><1|} on site q, each behind the centre move that brings it there.
+//
+// k_mps_kraus1: one 256-thread workgroup per (state, row).  Pass 1 strides over the site's
+// dims[p] x dims[p+1] block for rho00, rho11, rho01, reduced in a fixed order (wave butterfly, then
+// the four waves in index order through the LDS; no atomics: two calls return the same bits).
+// p_k = Re Tr(K_k^dag K_k rho) and the choice follow aqc_sv_traj_sample's rule, a measurement row
+// aqc_mps_sample's bit = [u (p0 + p1) >= p0].  Pass 2: Gamma^s <- sum_s' K_k[s][s'] / sqrt(p_k) Gamma^s'.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "mps_internal.h"
+#include "sample_rng.h"
+
+using aqc::cplx;
+using aqc::DevOp;
+using aqc::KrausJob;
+using aqc::TrajCtx;
+
+namespace {
+
+constexpr int kKT = 256;
+constexpr int kMaxShots = 1 << 30;
+constexpr int kMaxBatch = 256;
+// device memory the batch's MPS handles may take together (each: the Gammas, n 2 cap^2 complex, and
+// one two-site workspace per concurrent update of the widest wave)
+constexpr size_t kBatchBudgetBytes = (size_t)4 << 30;
+constexpr int kChunkRows = 64;  // schedule rows per run_waves call (bounds the job staging)
+int g_forced_batch = 0;
+
+__device__ __forceinline__ double wave_sum(double v) {
+  for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(kKT) void k_mps_kraus1(const KrausJob* __restrict__ jobs, const TrajCtx c) {
+  __shared__ double red[kKT / 64][4];
+  const KrausJob& j = jobs[blockIdx.x];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int cap = j.cap;
+  const int cl = min(j.dims[0], cap), cr = min(j.dims[1], cap);
+  const size_t half = (size_t)cap * cap;
+  double r00 = 0.0, r11 = 0.0, rx = 0.0, ry = 0.0;  // rho01 = sum w a0 conj(a1)
+  for (int e = tid; e < cl * cr; e += kKT) {
+    const int l = e / cr, r = e - l * cr;
+    const double wl = aqc::ldg(j.ll + l), wr = aqc::ldg(j.lr + r);
+    const double w = (wl * wl) * (wr * wr);
+    const size_t o = (size_t)l * cap + r;
+    const cplx a0 = aqc::ldg(j.g + o), a1 = aqc::ldg(j.g + half + o);
+    r00 = fma(w, aqc::cnorm2(a0), r00);
+    r11 = fma(w, aqc::cnorm2(a1), r11);
+    const cplx x = aqc::cmulc(a0, a1);
+    rx = fma(w, x.x, rx);
+    ry = fma(w, x.y, ry);
+  }
+  r00 = wave_sum(r00);
+  r11 = wave_sum(r11);
+  rx = wave_sum(rx);
+  ry = wave_sum(ry);
+  if (lane == 0) {
+    red[wave][0] = r00;
+    red[wave][1] = r11;
+    red[wave][2] = rx;
+    red[wave][3] = ry;
+  }
+  __syncthreads();
+  // every thread takes the same sums in the same order, so all choose the same k
+  r00 = r11 = rx = ry = 0.0;
+  for (int w = 0; w < kKT / 64; ++w) {
+    r00 += red[w][0];
+    r11 += red[w][1];
+    rx += red[w][2];
+    ry += red[w][3];
+  }
+  const int local = j.shot - c.shot0;
+  const int idx = j.meas ? c.nev + j.slot : j.slot;
+  const double u = c.u ? aqc::ldg(c.u + (size_t)local * c.nper + idx)
+                       : aqc::sample_uniform(c.seed, c.run, (uint64_t)j.shot, (uint32_t)idx);
+  const int nk = j.nk;
+  double pk[4], P = 0.0;
+  for (int k = 0; k < 4; ++k) {
+    pk[k] = 0.0;
+    if (k < nk) {
+      const double* w = j.w + 4 * k;
+      pk[k] = fmax(0.0, w[0] * r00 + w[1] * r11 + 2.0 * (w[2] * rx + w[3] * ry));
+      P += pk[k];
+    }
+  }
+  const double target = u * P;
+  int k = -1;
+  if (j.meas) {
+    k = target >= pk[0] ? 1 : 0;
+  } else {
+    int lastnz = 0;
+    double cs = 0.0;
+    for (int q = 0; q < 4; ++q) {
+      if (q >= nk) break;
+      cs += pk[q];
+      if (pk[q] > 0.0) lastnz = q;
+      if (k < 0 && cs > target) k = q;
+    }
+    if (k < 0) k = lastnz;
+  }
+  double psel = 0.0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+    if (q == k) psel = pk[q];
+  const double sc = psel > 0.0 ? 1.0 / sqrt(psel) : 0.0;
+  const cplx* m = j.K + 4 * k;
+  const cplx m00 = aqc::cscale(m[0], sc), m01 = aqc::cscale(m[1], sc);
+  const cplx m10 = aqc::cscale(m[2], sc), m11 = aqc::cscale(m[3], sc);
+  for (int e = tid; e < cl * cr; e += kKT) {
+    const int l = e / cr, r = e - l * cr;
+    const size_t o = (size_t)l * cap + r;
+    const cplx a0 = aqc::ldg(j.g + o), a1 = aqc::ldg(j.g + half + o);
+    aqc::stg(j.g + o, aqc::cfma(m01, a1, aqc::cmul(m00, a0)));
+    aqc::stg(j.g + half + o, aqc::cfma(m11, a1, aqc::cmul(m10, a0)));
+  }
+  if (tid == 0) {
+    if (j.meas) {
+      // one state's rows are serial, so this workgroup alone touches the word now
+      uint64_t* word = c.out + (size_t)local * c.words + (j.slot >> 6);
+      if (k) *word = *word | ((uint64_t)1 << (j.slot & 63));
+    } else if (c.choices) {
+      c.choices[(size_t)local * c.nev + j.slot] = (uint8_t)k;
+    }
+  }
+}
+
+// ---- the site-level schedule -----------------------------------------------------------------
+enum { tGate = 0, tSwap = 1, tMove = 2, tOne = 3, tKraus = 4, tMeas = 5 };
+
+struct TrajSched {
+  std::vector<DevOp> ops;
+  std::vector<uint8_t> tag;
+  int nev = 0;
+};
+
+int fail(const std::string& msg) {
+  aqc::set_error("aqc_mps_traj_sample: " + msg);
+  return AQC_ERR_ARG;
+}
+
+// the program's rows as aqc_sv_traj_sample checks them (traj.hip, build_rows)
+int validate(int n, const aqc_op_t* prog, int nprog) {
+  for (int i = 0; i < nprog; ++i) {
+    const aqc_op_t& op = prog[i];
+    if (op.flags == 0) {
+      if (!(op.nq == 1 || op.nq == 2) || op.q0 < 0 || op.q0 >= n) return fail("gate row: bad qubits");
+      if (op.nq == 2 && (op.q1 < 0 || op.q1 >= n || op.q1 == op.q0)) return fail("gate row: bad qubits");
+    } else if (op.flags == AQC_OP_KRAUS1) {
+      if (op.nq != 1 || op.q0 < 0 || op.q0 >= n || op.q1 < 1 || op.q1 > 4) return fail("malformed Kraus row");
+      double s00 = 0.0, s11 = 0.0, sx = 0.0, sy = 0.0;
+      for (int k = 0; k < op.q1; ++k) {
+        const double* K = op.m + 8 * k;  // K00 K01 K10 K11 as (re, im)
+        for (int e = 0; e < 8; ++e)
+          if (!std::isfinite(K[e])) return fail("malformed Kraus row");
+        s00 += K[0] * K[0] + K[1] * K[1] + K[4] * K[4] + K[5] * K[5];
+        s11 += K[2] * K[2] + K[3] * K[3] + K[6] * K[6] + K[7] * K[7];
+        sx += K[0] * K[2] + K[1] * K[3] + K[4] * K[6] + K[5] * K[7];
+        sy += K[0] * K[3] - K[1] * K[2] + K[4] * K[7] - K[5] * K[6];
+      }
+      if (std::fabs(s00 - 1.0) > 1e-9 || std::fabs(s11 - 1.0) > 1e-9 || std::fabs(sx) > 1e-9 || std::fabs(sy) > 1e-9)
+        return fail("Kraus row: sum K^dag K is not the identity");
+    } else {
+      return fail("unknown row flags");
+    }
+  }
+  return AQC_OK;
+}
+
+struct Planner {
+  int n, a, b;  // every site < a left-orthonormal, every site > b right-orthonormal
+  std::vector<int> order, loc;
+  std::vector<DevOp> tmp;  // what the swap-left scheduler emits, before the centre moves go between
+  aqc::Scheduler sc;
+  TrajSched& out;
+
+  Planner(int n_, TrajSched& dst) : n(n_), a(n_), b(-1), order(n_), loc(n_), sc(n_, order, loc, tmp), out(dst) {
+    for (int i = 0; i < n; ++i) order[i] = loc[i] = i;
+  }
+
+  void push(const DevOp& d, int tag) {
+    out.ops.push_back(d);
+    out.tag.push_back((uint8_t)tag);
+  }
+
+  void update(const DevOp& d, int tag) {  // a two-site update whose precondition holds
+    push(d, tag);
+    const int p = d.p;
+    if (a < p + 2) a = p + 1;
+    if (b > p - 1) b = p;
+  }
+
+  void centre(int left, int right) {  // until a >= left and b <= right
+    DevOp id = DevOp();
+    id.kind = 2;
+    for (int e = 0; e < 4; ++e) id.m[5 * e] = aqc::hc(1, 0);
+    while (a < left) {
+      id.p = a;
+      update(id, tMove);
+    }
+    while (b > right) {
+      id.p = b - 1;
+      update(id, tMove);
+    }
+  }
+
+  void drain(bool last_is_gate) {
+    for (size_t i = 0; i < tmp.size(); ++i) {
+      const DevOp& d = tmp[i];
+      if (d.kind == 2) {
+        centre(d.p, d.p + 1);
+        update(d, last_is_gate && i + 1 == tmp.size() ? tGate : tSwap);
+      } else {
+        push(d, tOne);
+      }
+    }
+    tmp.clear();
+  }
+
+  void row(int p, int nk, const cplx* K, int slot, int meas) {
+    centre(p, p);
+    DevOp d = DevOp();
+    d.kind = 3;
+    d.p = p;
+    d.nk = nk;
+    d.slot = slot;
+    d.meas = meas;
+    for (int e = 0; e < 4 * nk; ++e) d.m[e] = K[e];
+    push(d, meas ? tMeas : tKraus);
+    a = b = p;
+  }
+
+  void run(const aqc_op_t* prog, int nprog) {
+    for (int i = 0; i < nprog; ++i) {
+      const aqc_op_t& op = prog[i];
+      if (op.flags == AQC_OP_KRAUS1) {
+        const int q = op.q0, nk = op.q1;
+        cplx K[16];
+        for (int e = 0; e < 4 * nk; ++e) K[e] = aqc::hc(op.m[2 * e], op.m[2 * e + 1]);
+        if (sc.has[q]) {  // K_k <- K_k P: exact for any K (folding P into a later update is not)
+          for (int k = 0; k < nk; ++k) aqc::mat2_mul(K + 4 * k, &sc.pend[4 * q], K + 4 * k);
+          sc.has[q] = 0;
+        }
+        row(loc[q], nk, K, out.nev++, 0);
+      } else if (op.nq == 1) {
+        sc.one(op.q0, op.m);
+      } else {
+        sc.two(op.q0, op.q1, op.m);
+        drain(true);
+      }
+    }
+    sc.flush();
+    drain(false);
+    sc.sort();
+    drain(false);
+    cplx proj[8];
+    for (int e = 0; e < 8; ++e) proj[e] = aqc::hc(e == 0 || e == 7 ? 1 : 0, 0);
+    for (int q = 0; q < n; ++q) row(q, 2, proj, q, 1);
+  }
+};
+
+int build_schedule(int n, const aqc_op_t* prog, int nprog, TrajSched& s) {
+  if (int rc = validate(n, prog, nprog)) return rc;
+  Planner pl(n, s);
+  pl.run(prog, nprog);
+  return AQC_OK;
+}
+
+// the most two-site updates of one wave, levelled as run_waves levels a chunk (mps.hip, level_ops)
+int max_width(const DevOp* ops, size_t count, int n) {
+  std::vector<int> last(n + 1, -1), per;
+  int width = 1;
+  for (size_t i = 0; i < count; ++i) {
+    const DevOp& op = ops[i];
+    int l;
+    if (op.kind == 2) {
+      l = std::max(last[op.p], last[op.p + 1]) + 1;
+      last[op.p] = last[op.p + 1] = l;
+      if ((int)per.size() <= l) per.resize(l + 1, 0);
+      width = std::max(width, ++per[l]);
+    } else {
+      l = last[op.p] + 1;
+      last[op.p] = l;
+    }
+  }
+  return width;
+}
+
+aqc::PerDevice<aqc::DevScratch> g_scr;
+using aqc::up256;
+
+struct Handles {
+  std::vector<aqc_mps_t> h;
+  ~Handles() {
+    for (aqc_mps_t x : h) aqc_mps_destroy(x);
+  }
+};
+
+}  // namespace
+
+int aqc::launch_kraus(const KrausJob* jobs, int nj, const TrajCtx& ctx, hipStream_t st) {
+  // each job: the site's two Gammas read twice and written once, the lambdas
+  KernelTimer::begin(st, "mps_kraus1", 0.0, 0.0);
+  hipLaunchKernelGGL(k_mps_kraus1, dim3(nj), dim3(kKT), 0, st, jobs, ctx);
+  KernelTimer::end(st);
+  AQC_CHECK_LAUNCH();
+  return AQC_OK;
+}
+
+extern "C" {
+
+int aqc_mps_traj_set_batch(int batch) {
+  AQC_REQUIRE(batch >= 0 && batch <= 4096, "aqc_mps_traj_set_batch: 0 (default) or 1 .. 4096");
+  g_forced_batch = batch;
+  return AQC_OK;
+}
+
+int aqc_mps_traj_plan(int n, const aqc_op_t* prog, int nprog, int* counts, aqc_op_t* sched, int sched_cap) {
+  AQC_REQUIRE(counts && nprog >= 0 && (prog || nprog == 0) && sched_cap >= 0 && (sched || sched_cap == 0),
+              "aqc_mps_traj_plan: bad argument");
+  AQC_REQUIRE(n >= 1 && n <= 4096, "aqc_mps_traj_plan: n must be in 1 .. 4096");
+  TrajSched s;
+  if (int rc = build_schedule(n, prog, nprog, s)) return rc;
+  for (int c = 0; c < 7; ++c) counts[c] = 0;
+  for (uint8_t t : s.tag) counts[t] += 1;
+  counts[6] = (int)s.ops.size();
+  const size_t nout = std::min<size_t>(s.ops.size(), (size_t)sched_cap);
+  for (size_t i = 0; i < nout; ++i) {
+    const DevOp& d = s.ops[i];
+    aqc_op_t& o = sched[i];
+    std::memset(&o, 0, sizeof(o));
+    o.q0 = d.p;
+    if (d.kind == 2) {
+      o.nq = 2;
+      o.q1 = d.p + 1;
+      std::memcpy(o.m, d.m, 16 * sizeof(cplx));
+    } else if (d.kind == 1) {
+      o.nq = 1;
+      std::memcpy(o.m, d.m, 4 * sizeof(cplx));
+    } else {
+      o.nq = 1;
+      o.q1 = d.meas ? d.slot : d.nk;
+      o.flags = d.meas ? AQC_OP_MEASURE1 : (AQC_OP_KRAUS1 | (d.slot << 8));
+      std::memcpy(o.m, d.m, 4 * (size_t)d.nk * sizeof(cplx));
+    }
+  }
+  return AQC_OK;
+}
+
+int aqc_mps_traj_sample(int n, int chi_cap, double threshold, int max_chi, const aqc_op_t* prog, int nprog, int nshots,
+                        uint64_t seed, uint64_t run, const double* u, uint64_t* out, uint8_t* choices) {
+  AQC_REQUIRE(out && nprog >= 0 && (prog || nprog == 0), "aqc_mps_traj_sample: null argument");
+  AQC_REQUIRE(n >= 1 && n <= 4096, "aqc_mps_traj_sample: n must be in 1 .. 4096");
+  AQC_REQUIRE(chi_cap >= 1 && chi_cap <= aqc::kMaxCap, "aqc_mps_traj_sample: chi_cap must be in [1, 1024]");
+  AQC_REQUIRE(nshots >= 1 && nshots <= kMaxShots, "aqc_mps_traj_sample: nshots must be in 1 .. 2^30");
+  TrajSched sch;
+  if (int rc = build_schedule(n, prog, nprog, sch)) return rc;
+  const int nev = sch.nev, nper = nev + n, words = (n + 63) / 64;
+  if (u)
+    for (size_t e = 0, nu = (size_t)nshots * nper; e < nu; ++e)
+      if (!(u[e] >= 0.0 && u[e] < 1.0)) return fail("u must lie in [0, 1)");
+  const bool want_choices = choices && nev > 0;
+  const size_t nrows = sch.ops.size();
+  // the batch: B trajectories as B handles
+  int width = 1;
+  for (size_t r0 = 0; r0 < nrows; r0 += kChunkRows)
+    width = std::max(width, max_width(sch.ops.data() + r0, std::min<size_t>(kChunkRows, nrows - r0), n));
+  const size_t cap = chi_cap;
+  const size_t per_state = ((size_t)n * 2 * cap * cap + (size_t)width * (4 * cap * cap + aqc::work_elems(cap))) * sizeof(cplx);
+  int B = (int)std::min<size_t>({(size_t)nshots, (size_t)kMaxBatch, std::max<size_t>(1, kBatchBudgetBytes / per_state)});
+  if (g_forced_batch > 0) B = std::min(nshots, g_forced_batch);
+  Handles hs;
+  hs.h.reserve(B);
+  for (int s = 0; s < B; ++s) {
+    aqc_mps_t h = nullptr;
+    if (int rc = aqc_mps_create(n, chi_cap, threshold, max_chi, &h)) return rc;
+    hs.h.push_back(h);
+  }
+  hipStream_t st = aqc::mps_stream();
+  const size_t ub = u ? up256((size_t)B * nper * sizeof(double)) : 0;
+  const size_t ob = up256((size_t)B * words * sizeof(uint64_t));
+  const size_t cb = want_choices ? up256((size_t)B * nev) : 0;
+  AQC_HIP_CHECK(hipStreamSynchronize(st));  // (the scratch may be regrown)
+  aqc::DevScratch& scr = g_scr.here();
+  if (int rc = scr.ensure(ub + ob + cb)) return rc;
+  TrajCtx ctx;
+  std::memset(&ctx, 0, sizeof(ctx));
+  ctx.seed = seed;
+  ctx.run = run;
+  ctx.u = u ? (const double*)scr.dev : nullptr;
+  ctx.out = (uint64_t*)(scr.dev + ub);
+  ctx.choices = want_choices ? (uint8_t*)(scr.dev + ub + ob) : nullptr;
+  ctx.nev = nev;
+  ctx.nper = nper;
+  ctx.words = words;
+  std::vector<std::vector<DevOp>> lists;
+  for (int shot0 = 0; shot0 < nshots; shot0 += B) {
+    const int nb = std::min(B, nshots - shot0);
+    ctx.shot0 = shot0;
+    if (shot0 > 0)
+      for (int s = 0; s < nb; ++s)
+        if (int rc = aqc::mps_reset_zero(hs.h[s])) return rc;
+    AQC_HIP_CHECK(hipMemsetAsync(ctx.out, 0, (size_t)nb * words * sizeof(uint64_t), st));
+    if (u)
+      AQC_HIP_CHECK(hipMemcpyAsync(scr.dev, u + (size_t)shot0 * nper, (size_t)nb * nper * sizeof(double),
+                                   hipMemcpyHostToDevice, st));
+    for (size_t r0 = 0; r0 < nrows; r0 += kChunkRows) {
+      const size_t r1 = std::min(nrows, r0 + kChunkRows);
+      lists.assign(nb, std::vector<DevOp>(sch.ops.begin() + r0, sch.ops.begin() + r1));
+      if (int rc = aqc::run_waves(hs.h.data(), nb, lists, &ctx)) return rc;
+    }
+    // waits for the batch and reads its flags: a capacity overflow ends the call
+    if (int rc = aqc_mps_check_batch(hs.h.data(), nb)) return rc;
+    AQC_HIP_CHECK(hipMemcpyAsync(out + (size_t)shot0 * words, ctx.out, (size_t)nb * words * sizeof(uint64_t),
+                                 hipMemcpyDeviceToHost, st));
+    if (want_choices)
+      AQC_HIP_CHECK(hipMemcpyAsync(choices + (size_t)shot0 * nev, ctx.choices, (size_t)nb * nev, hipMemcpyDeviceToHost, st));
+    AQC_HIP_CHECK(hipStreamSynchronize(st));
+  }
+  return AQC_OK;
+}
+
+}  // extern "C"

@@ -294,6 +294,52 @@ def trajectory_sample(n, rows, n_events, shots, seed, run=0, u=None, return_choi
     return (out, choices) if return_choices else out
 
 
+def mps_trajectory_sample(n, rows, n_events, shots, seed, run=0, u=None, return_choices=False, chi_cap=64,
+                          threshold=1e-16, max_chi=None):
+    """``shots`` noisy shots as quantum trajectories on the MPS engine (aqc_mps_traj_sample):
+    uint64[shots, (n + 63) // 64] outcome words (bit q % 64 of word q // 64 = qubit q, DeviceMPS.sample's
+    format) of the program ``rows`` (noise.trajectory_program) on n qubits, whose Kraus rows number
+    ``n_events``.  Every trajectory is an MPS of capacity ``chi_cap`` truncated by (``threshold``,
+    ``max_chi``); one that outgrows the capacity raises the capacity AqcError.  ``u``: [shots,
+    n_events + n] uniforms in [0, 1) used instead of the generator's (event e in column e, qubit q's
+    measurement in column n_events + q).  With ``return_choices`` also the uint8[shots, n_events] Kraus
+    operator chosen at every event."""
+    shots, n_events, n = int(shots), int(n_events), int(n)
+    rows = np.ascontiguousarray(rows, dtype=_lib.OP_DTYPE)
+    if int(np.count_nonzero(rows["flags"] == _lib.OP_KRAUS1)) != n_events:
+        raise ValueError("mps_trajectory_sample: n_events does not match the program's Kraus rows")
+    out = np.zeros((max(shots, 0), (max(n, 1) + 63) // 64), dtype=np.uint64)
+    up = _uniforms_arg(u, (shots, n_events + n))
+    choices = np.zeros((max(shots, 0), n_events), dtype=np.uint8) if return_choices else None
+    _lib.check(_lib.lib().aqc_mps_traj_sample(n, int(chi_cap), float(threshold), int(max_chi or 0),
+                                              _lib.ptr(rows) if len(rows) else None, len(rows), shots, _u64(seed),
+                                              _u64(run), _lib.ptr(up), _lib.ptr(out),
+                                              _lib.ptr(choices) if return_choices and n_events else None))
+    return (out, choices) if return_choices else out
+
+
+MPS_TRAJECTORY_COUNTS = ("gate_updates", "swap_updates", "centre_moves", "one_site_rows", "kraus_rows",
+                         "measure_rows", "rows")
+
+
+def mps_trajectory_plan(n, rows, return_schedule=False):
+    """The site-level schedule every shot of ``mps_trajectory_sample`` runs (aqc_mps_traj_plan; no GPU):
+    a dict of the row counts named in MPS_TRAJECTORY_COUNTS (a two-site update is a gate, swap or
+    centre-move row), and with ``return_schedule`` also the rows themselves as an OP_DTYPE array
+    (``q0`` the site; flags 0 unitary, ``flags & 0xff == OP_KRAUS1`` a Kraus row with its event index
+    in ``flags >> 8``, OP_MEASURE1 the measurement of qubit ``q1``; see include/aqc_hip.h)."""
+    rows = np.ascontiguousarray(rows, dtype=_lib.OP_DTYPE)
+    counts = np.zeros(7, dtype=np.int32)
+    prog = _lib.ptr(rows) if len(rows) else None
+    _lib.check(_lib.load().aqc_mps_traj_plan(int(n), prog, len(rows), _lib.ptr(counts), None, 0))
+    named = dict(zip(MPS_TRAJECTORY_COUNTS, (int(c) for c in counts)))
+    if not return_schedule:
+        return named
+    sched = np.zeros(int(counts[6]), dtype=_lib.OP_DTYPE)
+    _lib.check(_lib.load().aqc_mps_traj_plan(int(n), prog, len(rows), _lib.ptr(counts), _lib.ptr(sched), len(sched)))
+    return named, sched
+
+
 def counts_from_samples(samples, n, clbit_of_qubit=None):
     """Counts dict of qiskit bitstrings (highest bit leftmost) from sampler output: uint64[shots]
     basis indices (n <= 64) or uint64[shots, words] packed words.  ``clbit_of_qubit``: {qubit:

@@ -1,5 +1,6 @@
 """Noise models for the shot backend: one-qubit Kraus channels attached to instruction names, and the
-flat program the device's trajectory sampler runs (csrc/traj.hip, aqc_sv_traj_sample).
+flat program the device's trajectory samplers run (csrc/traj.hip, aqc_sv_traj_sample, on a statevector;
+csrc/mps_traj.hip, aqc_mps_traj_sample, on an MPS).
 
 Stands in for the parts of ``qiskit_aer.noise`` that the reference uses
 (``execute_kwargs={'noise_model': NoiseModel, 'shots': ...}``, approximate_compiler.py:93;

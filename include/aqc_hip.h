@@ -38,7 +38,7 @@ typedef struct aqc_op {
   int32_t nq;
   int32_t q0;
   int32_t q1;
-  int32_t flags; /* 0: a gate; AQC_OP_KRAUS1: a Kraus row of aqc_sv_traj_sample only */
+  int32_t flags; /* 0: a gate; AQC_OP_KRAUS1: a Kraus row of aqc_sv_traj_sample / aqc_mps_traj_sample only */
   double m[32];
 } aqc_op_t;
 
@@ -175,6 +175,45 @@ int aqc_mps_sample(aqc_mps_t h, int nshots, uint64_t seed, uint64_t run, const d
 #define AQC_OP_KRAUS1 1
 int aqc_sv_traj_sample(int n, const aqc_op_t* prog, int nprog, int nshots, uint64_t seed, uint64_t run,
                        const double* u, uint64_t* out, uint8_t* choices);
+
+/* ---- noisy shot sampling above 24 qubits: quantum trajectories on the MPS engine -----------------
+   (Aer's qasm_simulator with method="matrix_product_state" under a NoiseModel.)
+   prog: aqc_sv_traj_sample's program.  Per shot: an MPS |0...0> of capacity chi_cap with the
+   truncation (threshold, max_chi) of aqc_mps_create, the gate rows as the engine's two-site updates
+   (swap-left routing, one-qubit gates deferred), each Kraus row at the orthogonality centre, then the
+   qubits sorted and measured one by one, q = 0 .. n-1.  The schedule keeps the centre on the host (two
+   integers, independent of the state) and moves it by identity-gate two-site updates, so the one-site
+   reduced density matrix rho[s][s'] = sum_{l,r} lambda_p[l]^2 lambda_{p+1}[r]^2 Gamma_p^s[l][r]
+   conj(Gamma_p^s'[l][r]) is exact wherever it is used: the law of the counts is the channel's.
+   Kraus event e: p_k = Re Tr(K_k^dag K_k rho) and aqc_sv_traj_sample's choice rule with u_e, then
+   Gamma^s <- sum_s' K_k[s][s'] / sqrt(p_k) Gamma^s' (a pending one-qubit gate P of that qubit is
+   absorbed first, K_k <- K_k P).  Measurement of qubit q: bit = [u_{E+q} (rho00 + rho11) >= rho00]
+   (aqc_mps_sample's rule), then the projection.
+   out: nshots x ((n+63)/64) words in aqc_mps_sample's format.  choices: NULL, or nshots x E bytes.
+   u_i = sample_uniform(seed, run, shot, i) for i = 0 .. E+n-1 (events first, then the qubits); when u
+   is not NULL, u_i = u[shot (E+n) + i], host doubles in [0, 1).
+   The shots run in batches of B trajectories held as B internal MPS handles: B = min(nshots, 256,
+   what 4 GiB of device memory hold of them, at least 1).  A shot's result depends on (seed, run, shot)
+   only, not on B; no atomics in any reduction: two calls return the same bits.
+   AQC_ERR_ARG as aqc_sv_traj_sample (n < 1, a malformed row, sum K^dag K off the identity by more
+   than 1e-9, a u outside [0, 1), nshots outside 1 .. 2^30).  AQC_ERR_STATE ("capacity (chi_cap)
+   exceeded") when any trajectory outgrows chi_cap: no part of the output is valid then. */
+int aqc_mps_traj_sample(int n, int chi_cap, double threshold, int max_chi, const aqc_op_t* prog, int nprog,
+                        int nshots, uint64_t seed, uint64_t run, const double* u, uint64_t* out, uint8_t* choices);
+/* Host planning of aqc_mps_traj_sample only (no GPU): the site-level schedule every shot runs, the
+   final sort and the measurement sweep included, as up to sched_cap rows in sched (NULL with
+   sched_cap 0 to count only).  q0 is the site.  flags == 0: a unitary row -- nq = 2: a two-site update
+   on sites (q0, q0 + 1) = q1, m the 4x4 matrix in site order (index 2 s_q0 + s_{q0+1}) with the
+   pending one-qubit gates folded in (routing swaps and centre moves are such rows, a centre move
+   carrying the identity); nq = 1: a flushed one-qubit gate.  (flags & 0xff) == AQC_OP_KRAUS1: a Kraus
+   row, q1 operators in m after folding, the event index in flags >> 8.  flags == AQC_OP_MEASURE1: the
+   measurement of qubit q1 (= q0, the qubits being sorted), m = {|0><0|, |1><1|}.
+   counts[7]: gate updates, routing / sorting swap updates, centre-move updates, one-site unitary
+   rows, Kraus rows, measurement rows, all rows. */
+#define AQC_OP_MEASURE1 2
+int aqc_mps_traj_plan(int n, const aqc_op_t* prog, int nprog, int* counts, aqc_op_t* sched, int sched_cap);
+/* Debugging: forces the batch size B of aqc_mps_traj_sample (1 .. 4096; 0 restores the default). */
+int aqc_mps_traj_set_batch(int batch);
 
 /* ---- Pauli-string expectation values: replaces circuit_operations_pauli_ops.py:60-100 -------------
    (expectation_value_of_pauli_operator, which runs one rotated circuit per term).
