@@ -303,19 +303,31 @@ class QiskitSamplingBackend(AQCBackend):
 
     A ``noise_model`` in the compiler's ``execute_kwargs`` reaches ``SamplingSimulator.run`` with every
     cost, <Z> and ``"circuits"`` tomography evaluation; ``"device"`` tomography is pure-state and
-    raises when it is given one.
+    raises when it is given one, unless ``trajectory_tomography`` is set.
+
+    ``trajectory_tomography`` (needs ``tomography="device"``): under a noise model with an effective
+    error, ``pair_tomography`` runs 9 x shots quantum trajectories of the circuit and reads every pair
+    out of each (aqc_sv_traj_pair_tomo): trajectory 9 i + s serves Pauli setting s of every pair, the
+    errors the model attaches to the appended ``sdg`` / ``h`` / ``measure`` folded into POVM effects
+    (noise.readout_effects).  A pair's nine tables have the law of the reference's nine noisy circuits;
+    tables of different pairs share trajectories and are correlated, which the per-pair fit never
+    sees.  Opt-in, because the sweep costs 9 x shots trajectories.  Statevector trajectories only (at
+    most 24 qubits); the concurrence lower bound stays noiseless-only.
     """
 
     TOMOGRAPHY_MODES = (None, "circuits", "device")
 
-    def __init__(self, simulator=None, tomography=None):
+    def __init__(self, simulator=None, tomography=None, trajectory_tomography=False):
         if tomography not in self.TOMOGRAPHY_MODES:
             raise ValueError(f"tomography must be one of {self.TOMOGRAPHY_MODES}")
+        if trajectory_tomography and tomography != "device":
+            raise TypeError("trajectory_tomography=True needs tomography='device'")
         self.simulator = simulator if simulator is not None else SamplingSimulator()
         if tomography == "device" and not isinstance(self.simulator, SamplingSimulator):
             raise TypeError("tomography='device' needs a SamplingSimulator (its cached device state); "
                             "use tomography='circuits' with other simulators")
         self.tomography = tomography
+        self.trajectory_tomography = bool(trajectory_tomography)
 
     # -- pair tomography ---------------------------------------------------------------
     def _require_tomography(self):
@@ -323,10 +335,38 @@ class QiskitSamplingBackend(AQCBackend):
             raise NotImplementedError("this QiskitSamplingBackend was built without tomography: pass "
                                       "tomography='device' or 'circuits'")
 
-    def _require_noiseless_device_route(self, kwargs):
+    def _require_noiseless_device_route(self, kwargs, what="pair tomography"):
         if self.tomography == "device" and kwargs.get("noise_model") is not None:
-            raise NotImplementedError("tomography='device' takes the pairs' RDMs from the pure state and cannot "
-                                      "honour a noise_model: use tomography='circuits'")
+            if what == "pair tomography":
+                hint = ("build the backend with trajectory_tomography=True (9 x shots noisy trajectories per "
+                        "sweep), or use tomography='circuits'")
+            else:
+                hint = "use tomography='circuits'"
+            raise NotImplementedError(f"tomography='device' takes the pairs' RDMs from the pure state and cannot "
+                                      f"honour a noise_model for {what}: {hint}")
+
+    def _noisy_tomography_program(self, circuit, noise_model):
+        """(rows, n_events, effects) of the noisy device route, or None when ``noise_model`` has no
+        effective error on the circuit or on the readout (the pure-state route then)."""
+        from ..noise import readout_effects, trajectory_program
+
+        if noise_model is None:
+            return None
+        n = circuit.num_qubits
+        base = without_classical_operations(circuit)
+        rows, n_events, _ = trajectory_program(base, noise_model)
+        readout = any(noise_model.channels(name, (q,)) for name in ("sdg", "h", "measure") for q in range(n))
+        if n_events == 0 and not readout:
+            return None
+        sim = self.simulator
+        method = sim.options.method
+        if method == "matrix_product_state":
+            raise NotImplementedError("trajectory_tomography runs statevector trajectories: a noise_model with "
+                                      "method 'matrix_product_state' is not supported")
+        if n > sim.MAX_NOISY_QUBITS:
+            raise NotImplementedError(f"trajectory_tomography runs statevector trajectories, which stop at "
+                                      f"{sim.MAX_NOISY_QUBITS} qubits (method {method!r}, {n} qubits)")
+        return rows, n_events, readout_effects(n, noise_model)
 
     def _seed_and_run(self, kwargs):
         """(seed, run) of one device sweep: ``seed_simulator`` alone when given, else the
@@ -341,12 +381,22 @@ class QiskitSamplingBackend(AQCBackend):
         """(rho [npairs, 4, 4], measures [npairs] or None) of the state ``circuit`` prepares, from
         ``execute_kwargs["shots"]`` shots per Pauli setting.  ``measure``: a name of
         device.EM_METHOD_CODES.  RDM index 2 bit_hi + bit_lo with hi the pair's larger qubit."""
-        from ..device import entanglement_measures, pair_tomography, tomo_fit
+        from ..device import entanglement_measures, pair_tomography, tomo_fit, trajectory_pair_tomography
 
         self._require_tomography()
         kwargs = dict(execute_kwargs or {})
-        self._require_noiseless_device_route(kwargs)
+        if not self.trajectory_tomography:
+            self._require_noiseless_device_route(kwargs)
         pairs = [(int(a), int(b)) for a, b in pairs]
+        noisy = self._noisy_tomography_program(circuit, kwargs.get("noise_model")) if self.trajectory_tomography else None
+        if noisy is not None:
+            if not pairs:
+                return np.zeros((0, 4, 4), dtype=complex), (None if measure is None else np.zeros(0))
+            seed, run = self._seed_and_run(kwargs)
+            counts = trajectory_pair_tomography(circuit.num_qubits, noisy[0], noisy[1], pairs, noisy[2],
+                                                int(kwargs.get("shots", 1024)), seed, run)
+            rho = tomo_fit(counts)
+            return rho, (None if measure is None else entanglement_measures(rho, measure))
         if self.tomography == "device":
             dev = self.simulator._state(circuit)  # (measures are not part of the cached state's key)
             rdms = dev.pair_rdms(pairs)
@@ -362,7 +412,7 @@ class QiskitSamplingBackend(AQCBackend):
 
         self._require_tomography()
         kwargs = dict(execute_kwargs or {})
-        self._require_noiseless_device_route(kwargs)
+        self._require_noiseless_device_route(kwargs, "the concurrence lower bound (its two-copy circuits)")
         pairs = [(int(a), int(b)) for a, b in pairs]
         if self.tomography == "device":
             dev = self.simulator._state(circuit)

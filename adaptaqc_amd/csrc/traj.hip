@@ -22,6 +22,15 @@
 //               in order; the first thread whose inclusive sum exceeds u_E P walks its amplitudes
 // No atomics anywhere: two calls return the same bits.
 //
+// Noisy pair tomography (aqc_sv_traj_pair_tomo) runs the same rows with another ending (the kernel's
+// END parameter): trajectory t serves Pauli setting s = t % 9 of every pair.  Instead of the final
+// draw, wave w takes pairs w, w + nwaves, ...: its lanes stride over the 2^(n-2) amplitude
+// quadruples of the pair and sum the 4 real and 6 complex entries of the pure state's 4x4 RDM, a
+// butterfly adds the lanes (no workgroup barrier, no LDS beside the state; the order depends on the
+// wave width only), and lane 0 forms p_o = max(0, Re Tr[(E_hi (x) E_lo) rho]) from the two qubits'
+// POVM effects of the setting and draws one outcome by the multinomial rule.  The count tables are
+// integer sums (integer atomics): they do not depend on the launch shape either.
+//
 // LDS layout: interleaved 16-byte complex amplitudes, as k_sv_segment's tile.  Split re / im arrays
 // (8-byte accesses) measured 2-7% slower at 8, 10, 12 and 13 qubits, with equal counts
 // (profiles/trajectory_layout_ab.json), and were removed.
@@ -48,6 +57,8 @@ constexpr size_t kMaxGlobalBytes = (size_t)512 << 20;
 
 enum { kGate1 = 0, kGate2 = 1, kKraus = 2 };
 enum { kLds = 0, kGlobal = 1 };
+enum { kEndDraw = 0, kEndPairs = 1 };  // a trajectory's ending: the full-register draw, or the pair readout
+constexpr int kMaxPairs = 4096;
 
 // A program row as the kernel reads it.  Gate: m = the 2x2 / 4x4 matrix.  Kraus: m[8k ..] = K_k,
 // w[4k ..] = (M00, M11, Re M01, Im M01) of M = K_k^dag K_k, ev = the event index.
@@ -62,11 +73,18 @@ constexpr int kRowWords = (int)(sizeof(TrajRow) / sizeof(double2));
 struct TrajJob {
   const TrajRow* prog;
   int nprog, n, nshots, nev;
-  const double* u;  // null, or nshots x (nev + 1)
+  const double* u;  // null, or nshots x ustride (nev + 1; nev + npairs for the pair readout)
   uint64_t seed, run;
   uint64_t* out;
   uint8_t* choices;  // null, or nshots x nev
   cplx* ws;          // kGlobal: 2^n amplitudes per workgroup
+  int ustride;
+  // kEndPairs (nshots then counts trajectories, trajectory t serving setting t % 9)
+  int npairs;
+  const int* pairs;               // 2 npairs
+  const double* effects;          // [n][3][2][4]: (E00, E11, Re E01, Im E01)
+  unsigned long long* counts;     // [npairs][9][4]
+  uint8_t* outcomes;              // null, or nshots x npairs
 };
 
 // bytes of dynamic LDS beside the state
@@ -102,7 +120,13 @@ __device__ __forceinline__ double wave_scan(double v, int lane) {
   return v;
 }
 
-template <int MODE>
+// entry (r, c) of the Hermitian 2x2 effect e = (E00, E11, Re E01, Im E01)
+__device__ __forceinline__ cplx effect_entry(const double* e, int r, int c) {
+  if (r == c) return aqc::cmk(e[r], 0.0);
+  return aqc::cmk(e[2], r < c ? e[3] : -e[3]);
+}
+
+template <int MODE, int END>
 __global__ __launch_bounds__(kMaxThreads) void k_sv_traj(const TrajJob j) {
   extern __shared__ double2 traj_lds[];
   const int tid = threadIdx.x, T = blockDim.x, lane = tid & 63, wave = tid >> 6, nwaves = T >> 6;
@@ -127,7 +151,7 @@ __global__ __launch_bounds__(kMaxThreads) void k_sv_traj(const TrajJob j) {
         ((double2*)rows)[w] = reinterpret_cast<const double2*>(j.prog + c0)[w];
       if (tid < nc && j.prog[c0 + tid].kind == kKraus) {
         const int e = j.prog[c0 + tid].ev;
-        ul[tid] = j.u ? j.u[(size_t)shot * (nev + 1) + e] : aqc::sample_uniform(j.seed, j.run, (uint64_t)shot, (uint32_t)e);
+        ul[tid] = j.u ? j.u[(size_t)shot * j.ustride + e] : aqc::sample_uniform(j.seed, j.run, (uint64_t)shot, (uint32_t)e);
       }
       for (int gi = 0; gi < nc; ++gi) {
         const TrajRow& r = rows[gi];
@@ -230,51 +254,124 @@ __global__ __launch_bounds__(kMaxThreads) void k_sv_traj(const TrajJob j) {
       }
     }
     __syncthreads();
-    // ---- the final draw ----
-    const int cpt = dim >= T ? dim / T : 1;  // contiguous amplitudes per thread
-    const int base = tid * cpt;
-    double s = 0.0;
-    int lastnz = -1;
-    if (base < dim)
-      for (int q = 0; q < cpt; ++q) {
-        const double p = aqc::cnorm2(psi.ld(base + q));
-        if (p > 0.0) lastnz = base + q;
-        s += p;
-      }
-    const double scan = wave_scan(s, lane);
-    int wl = lastnz;
-    for (int d = 1; d < 64; d <<= 1) wl = max(wl, __shfl_xor(wl, d, 64));
-    if (lane == 63) wtot[wave] = scan;
-    if (lane == 0) wlast[wave] = wl;
-    __syncthreads();
-    double off = 0.0, P = 0.0;
-    int last = -1;
-    for (int w = 0; w < nwaves; ++w) {
-      if (w == wave) off = P;
-      P += wtot[w];
-      last = max(last, wlast[w]);
-    }
-    const double uu = j.u ? j.u[(size_t)shot * (nev + 1) + nev]
-                          : aqc::sample_uniform(j.seed, j.run, (uint64_t)shot, (uint32_t)nev);
-    const double target = uu * P;
-    if (!(target < P)) {  // rounding (or the zero vector): the last outcome with p > 0
-      if (tid == 0) j.out[shot] = (uint64_t)(last < 0 ? 0 : last);
-    } else {
-      double prev = __shfl_up(scan, 1, 64);
-      if (lane == 0) prev = 0.0;
-      const double incl = off + scan, excl = off + prev;
-      if (incl > target && !(excl > target)) {  // the first thread whose inclusive sum exceeds the target
-        int idx = -1;
-        double c = excl;
-        for (int q = 0; q < cpt; ++q) {
-          c += aqc::cnorm2(psi.ld(base + q));
-          if (c > target) {
-            idx = base + q;
-            break;
+    if constexpr (END == kEndPairs) {
+      // ---- the pair readout: a wave per pair, setting s = shot % 9 ----
+      const int s9 = shot % 9;
+      for (int pj = wave; pj < j.npairs; pj += nwaves) {
+        const int qa = j.pairs[2 * pj], qb = j.pairs[2 * pj + 1];
+        const int lo = qa < qb ? qa : qb, hi = qa < qb ? qb : qa;
+        double d[4] = {0.0, 0.0, 0.0, 0.0};  // rho_ss
+        double ox[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, oy[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // rho_st, s < t
+        for (int p = lane; p < quarter; p += 64) {
+          const int b = insert_zero(insert_zero(p, lo), hi);
+          cplx a[4];
+#pragma unroll
+          for (int s = 0; s < 4; ++s) a[s] = psi.ld(b | ((s & 1) << lo) | ((s >> 1) << hi));
+          int c = 0;
+#pragma unroll
+          for (int s = 0; s < 4; ++s) {
+            d[s] += aqc::cnorm2(a[s]);
+#pragma unroll
+            for (int t = s + 1; t < 4; ++t, ++c) {
+              const cplx z = aqc::cmulc(a[s], a[t]);  // a_s conj(a_t)
+              ox[c] += z.x;
+              oy[c] += z.y;
+            }
           }
         }
-        if (idx < 0) idx = lastnz < 0 ? base : lastnz;
-        j.out[shot] = (uint64_t)idx;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) d[s] = wave_sum(d[s]);
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+          ox[c] = wave_sum(ox[c]);
+          oy[c] = wave_sum(oy[c]);
+        }
+        if (lane == 0) {
+          const double* eh = j.effects + (size_t)((hi * 3 + s9 / 3) * 2) * 4;
+          const double* el = j.effects + (size_t)((lo * 3 + s9 % 3) * 2) * 4;
+          double pk[4], P = 0.0;
+#pragma unroll
+          for (int o = 0; o < 4; ++o) {
+            const double* A = eh + 4 * (o >> 1);
+            const double* B = el + 4 * (o & 1);
+            // Tr(E rho) = sum_s E_ss rho_ss + 2 Re sum_{s<t} E_st conj(rho_st), E = A (x) B
+            double acc = 0.0;
+            int c = 0;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+              acc += A[s >> 1] * B[s & 1] * d[s];
+#pragma unroll
+              for (int t = s + 1; t < 4; ++t, ++c) {
+                const cplx e = aqc::cmul(effect_entry(A, s >> 1, t >> 1), effect_entry(B, s & 1, t & 1));
+                acc += 2.0 * (e.x * ox[c] + e.y * oy[c]);
+              }
+            }
+            pk[o] = fmax(0.0, acc);
+            P += pk[o];
+          }
+          const double uu = j.u ? j.u[(size_t)shot * j.ustride + nev + pj]
+                                : aqc::sample_uniform(j.seed, j.run, (uint64_t)shot, (uint32_t)(nev + pj));
+          const double target = uu * P;
+          int k = -1, lastnz = 0;
+          double c = 0.0;
+#pragma unroll
+          for (int o = 0; o < 4; ++o) {
+            c += pk[o];
+            if (pk[o] > 0.0) lastnz = o;
+            if (k < 0 && c > target) k = o;
+          }
+          if (k < 0) k = lastnz;
+          if (j.outcomes) j.outcomes[(size_t)shot * j.npairs + pj] = (uint8_t)k;
+          atomicAdd(j.counts + ((size_t)pj * 9 + s9) * 4 + k, 1ULL);
+        }
+      }
+    } else {
+      // ---- the final draw ----
+      const int cpt = dim >= T ? dim / T : 1;  // contiguous amplitudes per thread
+      const int base = tid * cpt;
+      double s = 0.0;
+      int lastnz = -1;
+      if (base < dim)
+        for (int q = 0; q < cpt; ++q) {
+          const double p = aqc::cnorm2(psi.ld(base + q));
+          if (p > 0.0) lastnz = base + q;
+          s += p;
+        }
+      const double scan = wave_scan(s, lane);
+      int wl = lastnz;
+      for (int d = 1; d < 64; d <<= 1) wl = max(wl, __shfl_xor(wl, d, 64));
+      if (lane == 63) wtot[wave] = scan;
+      if (lane == 0) wlast[wave] = wl;
+      __syncthreads();
+      double off = 0.0, P = 0.0;
+      int last = -1;
+      for (int w = 0; w < nwaves; ++w) {
+        if (w == wave) off = P;
+        P += wtot[w];
+        last = max(last, wlast[w]);
+      }
+      const double uu = j.u ? j.u[(size_t)shot * (nev + 1) + nev]
+                            : aqc::sample_uniform(j.seed, j.run, (uint64_t)shot, (uint32_t)nev);
+      const double target = uu * P;
+      if (!(target < P)) {  // rounding (or the zero vector): the last outcome with p > 0
+        if (tid == 0) j.out[shot] = (uint64_t)(last < 0 ? 0 : last);
+      } else {
+        double prev = __shfl_up(scan, 1, 64);
+        if (lane == 0) prev = 0.0;
+        const double incl = off + scan, excl = off + prev;
+        if (incl > target && !(excl > target)) {  // the first thread whose inclusive sum exceeds the target
+          int idx = -1;
+          double c = excl;
+          for (int q = 0; q < cpt; ++q) {
+            c += aqc::cnorm2(psi.ld(base + q));
+            if (c > target) {
+              idx = base + q;
+              break;
+            }
+          }
+          if (idx < 0) idx = lastnz < 0 ? base : lastnz;
+          j.out[shot] = (uint64_t)idx;
+        }
       }
     }
     __syncthreads();  // the draw has read the state before the next shot resets it
@@ -284,8 +381,10 @@ __global__ __launch_bounds__(kMaxThreads) void k_sv_traj(const TrajJob j) {
 aqc::PerDevice<aqc::DevScratch> g_scr;
 using aqc::up256;
 
+thread_local const char* t_entry = "aqc_sv_traj_sample";  // the entry point named in error messages
+
 int fail(const std::string& msg) {
-  aqc::set_error("aqc_sv_traj_sample: " + msg);
+  aqc::set_error(std::string(t_entry) + ": " + msg);
   return AQC_ERR_ARG;
 }
 
@@ -339,10 +438,46 @@ int threads_for(int n) {  // a quarter of the amplitudes, within 64 .. 512
   return std::max(64, std::min(kMaxThreads, t));
 }
 
-template <int MODE>
+// workgroups for ntraj trajectories of n qubits
+int grid_for(int n, int ntraj, int threads, int* grid) {
+  const size_t dim = (size_t)1 << n;
+  if (n <= kLdsMaxQubits) {
+    int dev = 0, cus = 0;
+    AQC_HIP_CHECK(hipGetDevice(&dev));
+    AQC_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    // workgroups that fit a CU together: LDS (160 KB), 32 waves, and at most 8
+    const size_t lds = dim * sizeof(cplx) + kSideBytes;
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>({(size_t)160 * 1024 / lds, (size_t)(2048 / threads), 8}));
+    *grid = (int)std::min<size_t>((size_t)ntraj, (size_t)std::max(cus, 1) * per_cu);
+  } else {
+    *grid = (int)std::max<size_t>(
+        1, std::min<size_t>({(size_t)ntraj, (size_t)kMaxGlobalWgs, kMaxGlobalBytes / (dim * sizeof(cplx))}));
+  }
+  return AQC_OK;
+}
+
+template <int MODE, int END>
 int launch(const TrajJob& j, int grid, int threads, size_t dyn) {
-  if (int e = aqc::allow_dynamic_lds((const void*)k_sv_traj<MODE>, (int)dyn)) return e;
-  hipLaunchKernelGGL(k_sv_traj<MODE>, dim3(grid), dim3(threads), dyn, 0, j);
+  if (int e = aqc::allow_dynamic_lds((const void*)k_sv_traj<MODE, END>, (int)dyn)) return e;
+  hipLaunchKernelGGL((k_sv_traj<MODE, END>), dim3(grid), dim3(threads), dyn, 0, j);
+  return AQC_OK;
+}
+
+// the Hermitian 2x2 effects [n][3][2][4]: finite, E0 + E1 = I within 1e-9, each PSD within 1e-12
+int check_effects(int n, const double* effects) {
+  for (int qb = 0; qb < n * 3; ++qb) {
+    const double* e0 = effects + (size_t)qb * 8;
+    const double* e1 = e0 + 4;
+    for (int c = 0; c < 8; ++c)
+      if (!std::isfinite(e0[c])) return fail("an effect is not finite");
+    if (std::fabs(e0[0] + e1[0] - 1.0) > 1e-9 || std::fabs(e0[1] + e1[1] - 1.0) > 1e-9 ||
+        std::fabs(e0[2] + e1[2]) > 1e-9 || std::fabs(e0[3] + e1[3]) > 1e-9)
+      return fail("the two effects of a qubit and basis do not sum to the identity");
+    for (const double* e : {e0, e1}) {
+      const double half_gap = std::hypot(0.5 * (e[0] - e[1]), std::hypot(e[2], e[3]));
+      if (0.5 * (e[0] + e[1]) - half_gap < -1e-12) return fail("an effect is not positive semidefinite");
+    }
+  }
   return AQC_OK;
 }
 
@@ -350,6 +485,7 @@ int launch(const TrajJob& j, int grid, int threads, size_t dyn) {
 
 extern "C" int aqc_sv_traj_sample(int n, const aqc_op_t* prog, int nprog, int nshots, uint64_t seed, uint64_t run,
                                   const double* u, uint64_t* out, uint8_t* choices) {
+  t_entry = "aqc_sv_traj_sample";
   AQC_REQUIRE(out && nprog >= 0 && (prog || nprog == 0), "aqc_sv_traj_sample: null argument");
   AQC_REQUIRE(n >= 1 && n <= kMaxQubits, "aqc_sv_traj_sample: n must be in 1 .. 24");
   AQC_REQUIRE(nshots >= 1 && nshots <= kMaxShots, "aqc_sv_traj_sample: nshots must be in 1 .. 2^30");
@@ -364,19 +500,8 @@ extern "C" int aqc_sv_traj_sample(int n, const aqc_op_t* prog, int nprog, int ns
   const size_t dim = (size_t)1 << n;
   const bool in_lds = n <= kLdsMaxQubits;
   const int threads = threads_for(n);
-  int grid;
-  if (in_lds) {
-    int dev = 0, cus = 0;
-    AQC_HIP_CHECK(hipGetDevice(&dev));
-    AQC_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    // workgroups that fit a CU together: LDS (160 KB), 32 waves, and at most 8
-    const size_t lds = dim * sizeof(cplx) + kSideBytes;
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>({(size_t)160 * 1024 / lds, (size_t)(2048 / threads), 8}));
-    grid = (int)std::min<size_t>((size_t)nshots, (size_t)std::max(cus, 1) * per_cu);
-  } else {
-    grid = (int)std::max<size_t>(
-        1, std::min<size_t>({(size_t)nshots, (size_t)kMaxGlobalWgs, kMaxGlobalBytes / (dim * sizeof(cplx))}));
-  }
+  int grid = 0;
+  if (int rc = grid_for(n, nshots, threads, &grid)) return rc;
   const size_t pb = up256(std::max<size_t>(1, rows.size()) * sizeof(TrajRow));
   const size_t ub = u ? up256(nu * sizeof(double)) : 0;
   const size_t ob = up256((size_t)nshots * sizeof(uint64_t));
@@ -394,6 +519,7 @@ extern "C" int aqc_sv_traj_sample(int n, const aqc_op_t* prog, int nprog, int ns
   j.n = n;
   j.nshots = nshots;
   j.nev = nev;
+  j.ustride = nev + 1;
   j.u = u ? (const double*)(buf + pb) : nullptr;
   j.seed = seed;
   j.run = run;
@@ -404,14 +530,90 @@ extern "C" int aqc_sv_traj_sample(int n, const aqc_op_t* prog, int nprog, int ns
     AQC_HIP_CHECK(hipMemcpyAsync(buf, rows.data(), rows.size() * sizeof(TrajRow), hipMemcpyHostToDevice, st));
   if (u) AQC_HIP_CHECK(hipMemcpyAsync(buf + pb, u, nu * sizeof(double), hipMemcpyHostToDevice, st));
   aqc::KernelTimer::begin(st, "sv_traj", 0.0, (double)nshots * (double)nprog * (double)dim * 14.0);
-  const int rc = in_lds ? launch<kLds>(j, grid, threads, dim * sizeof(cplx) + kSideBytes)
-                        : launch<kGlobal>(j, grid, threads, kSideBytes);
+  const int rc = in_lds ? launch<kLds, kEndDraw>(j, grid, threads, dim * sizeof(cplx) + kSideBytes)
+                        : launch<kGlobal, kEndDraw>(j, grid, threads, kSideBytes);
   aqc::KernelTimer::end(st);
   if (rc != AQC_OK) return rc;
   AQC_CHECK_LAUNCH();
   AQC_HIP_CHECK(hipMemcpyAsync(out, j.out, (size_t)nshots * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
   if (want_choices)
     AQC_HIP_CHECK(hipMemcpyAsync(choices, j.choices, (size_t)nshots * nev, hipMemcpyDeviceToHost, st));
+  AQC_HIP_CHECK(hipStreamSynchronize(st));
+  return AQC_OK;
+}
+
+extern "C" int aqc_sv_traj_pair_tomo(int n, const aqc_op_t* prog, int nprog, const int* pairs, int npairs,
+                                     const double* effects, int nshots, uint64_t seed, uint64_t run, const double* u,
+                                     int64_t* counts, uint8_t* outcomes) {
+  t_entry = "aqc_sv_traj_pair_tomo";
+  AQC_REQUIRE(counts && pairs && effects && nprog >= 0 && (prog || nprog == 0), "aqc_sv_traj_pair_tomo: null argument");
+  AQC_REQUIRE(n >= 2 && n <= kMaxQubits, "aqc_sv_traj_pair_tomo: n must be in 2 .. 24");
+  AQC_REQUIRE(npairs >= 1 && npairs <= kMaxPairs, "aqc_sv_traj_pair_tomo: npairs must be in 1 .. 4096");
+  AQC_REQUIRE(nshots >= 1 && nshots <= kMaxShots / 9, "aqc_sv_traj_pair_tomo: 9 nshots must be in 9 .. 2^30");
+  for (int p = 0; p < npairs; ++p) {
+    const int a = pairs[2 * p], b = pairs[2 * p + 1];
+    if (a < 0 || a >= n || b < 0 || b >= n || a == b) return fail("a pair needs two different qubits in 0 .. n-1");
+  }
+  if (int rc = check_effects(n, effects)) return rc;
+  std::vector<TrajRow> rows;
+  int nev = 0;
+  if (int rc = build_rows(n, prog, nprog, rows, &nev)) return rc;
+  const int ntraj = 9 * nshots;
+  const int ustride = nev + npairs;
+  const size_t nu = (size_t)ntraj * ustride;
+  if (u)
+    for (size_t e = 0; e < nu; ++e)
+      if (!(u[e] >= 0.0 && u[e] < 1.0)) return fail("u must lie in [0, 1)");
+  const size_t dim = (size_t)1 << n;
+  const bool in_lds = n <= kLdsMaxQubits;
+  const int threads = threads_for(n);
+  int grid = 0;
+  if (int rc = grid_for(n, ntraj, threads, &grid)) return rc;
+  const size_t pb = up256(std::max<size_t>(1, rows.size()) * sizeof(TrajRow));
+  const size_t ub = u ? up256(nu * sizeof(double)) : 0;
+  const size_t qb = up256((size_t)npairs * 2 * sizeof(int));
+  const size_t eb = up256((size_t)n * 24 * sizeof(double));
+  const size_t tb = up256((size_t)npairs * 36 * sizeof(int64_t));
+  const size_t ob = outcomes ? up256((size_t)ntraj * npairs) : 0;
+  const size_t wb = in_lds ? 0 : (size_t)grid * dim * sizeof(cplx);
+  hipStream_t st = nullptr;
+  AQC_HIP_CHECK(hipDeviceSynchronize());  // (the scratch may be regrown)
+  aqc::DevScratch& sc = g_scr.here();
+  if (int rc = sc.ensure(pb + ub + qb + eb + tb + ob + wb)) return rc;
+  char* buf = sc.dev;
+  TrajJob j;
+  std::memset(&j, 0, sizeof(j));
+  j.prog = (const TrajRow*)buf;
+  j.nprog = nprog;
+  j.n = n;
+  j.nshots = ntraj;
+  j.nev = nev;
+  j.ustride = ustride;
+  j.u = u ? (const double*)(buf + pb) : nullptr;
+  j.seed = seed;
+  j.run = run;
+  j.npairs = npairs;
+  j.pairs = (const int*)(buf + pb + ub);
+  j.effects = (const double*)(buf + pb + ub + qb);
+  j.counts = (unsigned long long*)(buf + pb + ub + qb + eb);
+  j.outcomes = outcomes ? (uint8_t*)(buf + pb + ub + qb + eb + tb) : nullptr;
+  j.ws = in_lds ? nullptr : (cplx*)(buf + pb + ub + qb + eb + tb + ob);
+  if (!rows.empty())
+    AQC_HIP_CHECK(hipMemcpyAsync(buf, rows.data(), rows.size() * sizeof(TrajRow), hipMemcpyHostToDevice, st));
+  if (u) AQC_HIP_CHECK(hipMemcpyAsync(buf + pb, u, nu * sizeof(double), hipMemcpyHostToDevice, st));
+  AQC_HIP_CHECK(hipMemcpyAsync((void*)j.pairs, pairs, (size_t)npairs * 2 * sizeof(int), hipMemcpyHostToDevice, st));
+  AQC_HIP_CHECK(hipMemcpyAsync((void*)j.effects, effects, (size_t)n * 24 * sizeof(double), hipMemcpyHostToDevice, st));
+  AQC_HIP_CHECK(hipMemsetAsync(j.counts, 0, (size_t)npairs * 36 * sizeof(int64_t), st));
+  aqc::KernelTimer::begin(st, "sv_traj_pair_tomo", 0.0,
+                          (double)ntraj * ((double)nprog * 14.0 + (double)npairs * 10.0) * (double)dim);
+  const int rc = in_lds ? launch<kLds, kEndPairs>(j, grid, threads, dim * sizeof(cplx) + kSideBytes)
+                        : launch<kGlobal, kEndPairs>(j, grid, threads, kSideBytes);
+  aqc::KernelTimer::end(st);
+  if (rc != AQC_OK) return rc;
+  AQC_CHECK_LAUNCH();
+  AQC_HIP_CHECK(hipMemcpyAsync(counts, j.counts, (size_t)npairs * 36 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  if (outcomes)
+    AQC_HIP_CHECK(hipMemcpyAsync(outcomes, j.outcomes, (size_t)ntraj * npairs, hipMemcpyDeviceToHost, st));
   AQC_HIP_CHECK(hipStreamSynchronize(st));
   return AQC_OK;
 }

@@ -294,6 +294,34 @@ def trajectory_sample(n, rows, n_events, shots, seed, run=0, u=None, return_choi
     return (out, choices) if return_choices else out
 
 
+def trajectory_pair_tomography(n, rows, n_events, pairs, effects, shots, seed, run=0, u=None, return_outcomes=False):
+    """Noisy tomography counts of every pair in one launch (aqc_sv_traj_pair_tomo): int64 [npairs, 9, 4],
+    ``shots`` per Pauli setting, of the program ``rows`` (noise.trajectory_program of the circuit without
+    its classical operations) whose Kraus rows number ``n_events``, measured with the POVM ``effects``
+    [n, 3, 2, 4] (noise.readout_effects).  9 ``shots`` trajectories run; trajectory t = 9 i + s serves
+    setting s = 3 b_hi + b_lo of every pair.  ``u``: [9 shots, n_events + npairs] uniforms in [0, 1) used
+    instead of the generator's (events first, then pairs).  With ``return_outcomes`` also the uint8
+    [9 shots, npairs] outcome o = 2 o_hi + o_lo every trajectory drew for every pair."""
+    n, shots, n_events = int(n), int(shots), int(n_events)
+    rows = np.ascontiguousarray(rows, dtype=_lib.OP_DTYPE)
+    if int(np.count_nonzero(rows["flags"] == _lib.OP_KRAUS1)) != n_events:
+        raise ValueError("trajectory_pair_tomography: n_events does not match the program's Kraus rows")
+    pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+    npairs = len(pr)
+    eff = np.ascontiguousarray(effects, dtype=np.float64)
+    if eff.shape != (n, 3, 2, 4):
+        raise ValueError(f"trajectory_pair_tomography: effects must have shape {(n, 3, 2, 4)}")
+    ntraj = 9 * max(shots, 0)
+    up = _uniforms_arg(u, (ntraj, n_events + npairs))
+    counts = np.zeros((npairs, 9, 4), dtype=np.int64)
+    outcomes = np.zeros((ntraj, npairs), dtype=np.uint8) if return_outcomes else None
+    _lib.check(_lib.lib().aqc_sv_traj_pair_tomo(n, _lib.ptr(rows) if len(rows) else None, len(rows),
+                                                _lib.ptr(pr) if npairs else None, npairs, _lib.ptr(eff), shots,
+                                                _u64(seed), _u64(run), _lib.ptr(up), _lib.ptr(counts),
+                                                _lib.ptr(outcomes) if return_outcomes and npairs else None))
+    return (counts, outcomes) if return_outcomes else counts
+
+
 def mps_trajectory_sample(n, rows, n_events, shots, seed, run=0, u=None, return_choices=False, chi_cap=64,
                           threshold=1e-16, max_chi=None):
     """``shots`` noisy shots as quantum trajectories on the MPS engine (aqc_mps_traj_sample):

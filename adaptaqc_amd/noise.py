@@ -1,6 +1,7 @@
 """Noise models for the shot backend: one-qubit Kraus channels attached to instruction names, and the
 flat program the device's trajectory samplers run (csrc/traj.hip, aqc_sv_traj_sample, on a statevector;
-csrc/mps_traj.hip, aqc_mps_traj_sample, on an MPS).
+csrc/mps_traj.hip, aqc_mps_traj_sample, on an MPS), and the POVM effects of a noisy Pauli-basis
+readout for noisy pair tomography (``readout_effects``, aqc_sv_traj_pair_tomo).
 
 Stands in for the parts of ``qiskit_aer.noise`` that the reference uses
 (``execute_kwargs={'noise_model': NoiseModel, 'shots': ...}``, approximate_compiler.py:93;
@@ -199,6 +200,44 @@ def kraus_row(error, qubit):
     row["nq"], row["q0"], row["q1"], row["flags"] = 1, int(qubit), len(error.kraus), _lib.OP_KRAUS1
     row["m"][0, : 8 * len(error.kraus)] = np.stack(error.kraus).reshape(-1).view(np.float64)
     return row
+
+
+_H = np.array([[1, 1], [1, -1]], dtype=complex) / np.sqrt(2)
+_SDG = np.diag([1.0 + 0j, -1j])
+
+
+def readout_effects(n, noise_model):
+    """float64 [n, 3, 2, 4]: the POVM effects of a noisy Pauli-basis measurement of every qubit, as
+    aqc_sv_traj_pair_tomo takes them -- entry [q, b, o] holds (E00, E11, Re E01, Im E01) of the
+    Hermitian 2x2 effect of qubit q, basis b (0 X, 1 Y, 2 Z), outcome o (0 the +1 eigenstate).
+
+    The reference measures basis Y by appending ``sdg``, ``h``, ``measure`` (X: ``h``, ``measure``;
+    Z: ``measure``), and under a noise model each of them carries the error attached to it on
+    ``(q,)``.  All are one-qubit operations on the measured qubit, so they fold into
+    E = Sdg^dag A_sdg( H^dag A_h( A_meas(|o><o|) ) H ) Sdg, with A_x(E) = sum_k K_k^dag E K_k the adjoint
+    of the channel ``noise_model.channels(x, (q,))`` (H / A_h for X and Y only, Sdg / A_sdg for Y only).
+    ``None`` or a model without these errors gives the projectors onto the Pauli eigenvectors."""
+
+    def adjoint(name, q, e):
+        if noise_model is None:
+            return e
+        for _, error in noise_model.channels(name, (q,)):
+            e = sum(k.conj().T @ e @ k for k in error.kraus)
+        return e
+
+    out = np.zeros((int(n), 3, 2, 4))
+    for q in range(int(n)):
+        for b in range(3):
+            for o in range(2):
+                e = np.zeros((2, 2), dtype=complex)
+                e[o, o] = 1.0
+                e = adjoint("measure", q, e)
+                if b < 2:
+                    e = _H.conj().T @ adjoint("h", q, e) @ _H
+                if b == 1:
+                    e = _SDG.conj().T @ adjoint("sdg", q, e) @ _SDG
+                out[q, b, o] = (e[0, 0].real, e[1, 1].real, e[0, 1].real, e[0, 1].imag)
+    return out
 
 
 def trajectory_program(circuit, noise_model):

@@ -176,6 +176,33 @@ int aqc_mps_sample(aqc_mps_t h, int nshots, uint64_t seed, uint64_t run, const d
 int aqc_sv_traj_sample(int n, const aqc_op_t* prog, int nprog, int nshots, uint64_t seed, uint64_t run,
                        const double* u, uint64_t* out, uint8_t* choices);
 
+/* ---- noisy pair tomography: the nine Pauli settings of every pair under a noise model -------------
+   What the reference measures when it runs a pair's nine rotated circuits under a NoiseModel
+   (entanglement_measures.py:101-135), as one launch.  prog: aqc_sv_traj_sample's program (the circuit
+   without its classical operations), same validation, same event numbering (E Kraus rows).
+   pairs: 2 npairs ints, a != b in 0 .. n-1, either way round; used as hi = max, lo = min.
+   effects: n x 3 x 2 x 4 doubles, entry [((q 3 + b) 2 + o) 4 + c] = (E00, E11, Re E01, Im E01) of the
+   Hermitian 2x2 POVM effect of qubit q, basis b (0 X, 1 Y, 2 Z), outcome o: everything the reference
+   appends after the circuit (sdg, h, measure, each with its error) folded into the measurement.
+   ntraj = 9 nshots trajectories; trajectory t = 9 i + s serves setting s = 3 b_hi + b_lo of EVERY
+   pair.  Its rows run as in aqc_sv_traj_sample; then for pair j: rho = the 4x4 RDM of the pure
+   trajectory state (index 2 bit_hi + bit_lo), p_o = max(0, Re Tr[(E[hi][b_hi][o_hi] (x)
+   E[lo][b_lo][o_lo]) rho]) for o = 2 o_hi + o_lo, and one outcome by aqc_multinomial_counts' rule
+   (the smallest o with C_o > u P, else the last o with p_o > 0) with u = sample_uniform(seed, run, t,
+   E + j).  One trajectory and one draw from that trajectory's p is one shot of the reference's
+   circuit; the nine tables of a pair come from disjoint trajectories, so a pair's [9][4] table has the
+   reference's joint law.  Tables of different pairs share trajectories and are correlated.
+   u, when not NULL: ntraj x (E + npairs) host doubles in [0, 1), events first, then pairs.
+   counts[(j 9 + s) 4 + o]: host int64, every row sums to nshots.  outcomes: NULL, or ntraj x npairs
+   bytes, the drawn o.  An outcome depends on (seed, run, t) only: fewer shots give a prefix.  The
+   RDM sums run in a fixed order and the counts are integer sums (integer atomics; no floating-point
+   atomics): two calls return the same bits.  State placement as aqc_sv_traj_sample.
+   AQC_ERR_ARG: as aqc_sv_traj_sample; n outside 2 .. 24, npairs outside 1 .. 4096, 9 nshots above
+   2^30, a bad pair, or an effect that is not finite, whose pair does not sum to I within 1e-9, or
+   that is not positive semidefinite within 1e-12. */
+int aqc_sv_traj_pair_tomo(int n, const aqc_op_t* prog, int nprog, const int* pairs, int npairs, const double* effects,
+                          int nshots, uint64_t seed, uint64_t run, const double* u, int64_t* counts, uint8_t* outcomes);
+
 /* ---- noisy shot sampling above 24 qubits: quantum trajectories on the MPS engine -----------------
    (Aer's qasm_simulator with method="matrix_product_state" under a NoiseModel.)
    prog: aqc_sv_traj_sample's program.  Per shot: an MPS |0...0> of capacity chi_cap with the
