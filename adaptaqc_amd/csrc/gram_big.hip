@@ -62,7 +62,6 @@ __device__ unsigned long long g_gbig_ticks[9];
 namespace {
 
 constexpr double kGbRelFloor = 1e-9;
-constexpr double kGbClusterGap = 1e-5;  // k_gb_gs: eigenvalues closer than this times ||T|| share a cluster
 constexpr unsigned long long kSpinTicks = 10000000ull;  // s_memrealtime (100 MHz): 100 ms
 // the counter-wait limit in force (aqc_gb_set_spin_limit: tests force the timeout decline with 0)
 unsigned long long g_gb_spin = kSpinTicks;
@@ -971,10 +970,10 @@ __global__ __launch_bounds__(64) void k_gb_inv(const TwoSiteJob* __restrict__ jo
   if (jb == 0 && i == 0) atomicAdd(&g_gbig_ticks[7], __builtin_amdgcn_s_memtime() - t_start);
 }
 
-// ---- Gram-Schmidt inside clusters (eigenvalue gaps below kGbClusterGap ||T||), then the cluster
+// ---- Gram-Schmidt inside clusters (eigenvalue gaps below aqc::kGramClusterGap ||T||), then the cluster
 // members' sigma^2 again: grid (nj), 256 threads ----
 // Inverse iteration alone leaves two vectors orthogonal to ~eps ||T|| / gap.  With clusters only below
-// 1e-7 ||T|| (the 2 chi = 128 path's rule) pairs at 3e-7 ||T|| and the small sigma^2 of a graded
+// 1e-7 ||T|| (the 2 chi = 128 path's rule until it took this one) pairs at 3e-7 ||T|| and the small sigma^2 of a graded
 // spectrum, whose absolute gaps are as small, came out with |V^H V - I| up to 1.2e-10
 // (tests/test_gpu_big_svd.py: `pairs`, `clusters` at K = C); at 1e-5 ||T|| the same inputs give
 // 6e-14 and config 5's wave costs the same (40-60 of its 256 kept vectors per job are then cluster
@@ -998,7 +997,7 @@ __global__ __launch_bounds__(256) void k_gb_gs(const TwoSiteJob* __restrict__ jo
   K = kept_count(a, jb);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const double* lam = a.lam + (size_t)jb * CT;
-  const double ortol = kGbClusterGap * ldg(a.tn + jb);
+  const double ortol = kGramClusterGap * ldg(a.tn + jb);
   double* zb = a.z + (size_t)jb * CT * CT;
   const double* dd = a.d + (size_t)jb * CT;
   const double* ee = a.e + (size_t)jb * CT;

@@ -80,6 +80,10 @@ double g_jacobi_tol_factor = 1.0;
 // Sweep stop of the register Jacobi: after a sweep whose counted rotations all had |t| <= this,
 // the remaining off-diagonal is O(t^2) (quadratic convergence) and no further sweep is run.
 constexpr double kDefaultTinyT = 1e-6;
+// ... and whose counted rotations were all between columns at a cosine of at most this, for the
+// first kStopCosSweeps sweeps (jacobi_reg_body)
+constexpr double kStopCos = 3e-13;
+constexpr int kStopCosSweeps = 30;
 double g_jacobi_tiny_t = kDefaultTinyT;
 // dot-product noise floor of the Jacobi rotations, in units of eps ||W|| (|a| + |b|): off (a
 // floor costs graded matrices their small singular vectors)
@@ -569,9 +573,9 @@ __device__ __forceinline__ void jacobi_reg_body(const TwoSiteJob& j) {
     xscl[g] = 1.0;
   }
   // Stop rule: a sweep whose counted rotations all moved at most jtiny^2 (default 1e-12) of their
-  // pair's squared norms (t|g| <= jtiny^2 (|a|^2 + |b|^2)) is the last: the next sweep would move
-  // them by less again (quadratic convergence), so the confirming sweep with no rotation at all is
-  // skipped.
+  // pair's squared norms (t|g| <= jtiny^2 (|a|^2 + |b|^2)), between columns at a cosine of at most
+  // kStopCos, is the last: the next sweep would move them by less again, so the confirming sweep with
+  // no rotation at all is skipped.
   const double tiny2 = j.jtiny * j.jtiny;
   double sd = 1.0, sn = 0.0;  // S: scale and tracked squared norm (uniform in the group)
   int sweeps = 0;
@@ -650,7 +654,16 @@ __device__ __forceinline__ void jacobi_reg_body(const TwoSiteJob& j) {
             // (t|g| ~ t^2 (|a|^2 - |b|^2) for separated pairs -- |t| > jtiny -- and ~ |g| for a
             // (near-)degenerate pair, whose t stays O(1) at any |g|: a test on |t| alone stopped
             // with |g| ~ 1e-6 |a|^2 - |b|^2| left, 3e-8 errors in a degenerate pair's sigma)
-            if (fabs(te) * g2 > tiny2 * (sn + mn)) my_big = 1;
+            // The moved mass is relative to the larger norm: between a large column and a small one
+            // it stays below jtiny^2 up to a cosine |g| / (|a| |b|) of jtiny |a| / |b|, and a rotation
+            // inside a degenerate plateau moves none at any angle while it carries what one of its
+            // columns still has against a large column into the other (sigma = 0.6 against a plateau
+            // at 6e-5: |V^H V - I| = 1.9e-7, ||theta_dev - theta_K|| = 2e-7, tests/test_gpu_small_svd.py
+            // `plateau`).  So a rotation also counts while the pair's cosine is above kStopCos: the
+            // last sweep then saw every pair at or below it.  (Not after kStopCosSweeps sweeps: a
+            // pair whose cosine never settles there must not keep the loop running.)
+            if (fabs(te) * g2 > tiny2 * (sn + mn) || (sweeps < kStopCosSweeps && g2 > kStopCos * kStopCos * sn * mn))
+              my_big = 1;
           }
           const double ra = md * isd, ira = sd * imd;  // d_b / d_a and its inverse
           const double mux = te * gx * ra, muy = -te * gy * ra;   // mu = t conj(e) d_b / d_a

@@ -163,6 +163,9 @@ __device__ __forceinline__ void jacobi_te(double al, double be, double g2, doubl
 }
 
 constexpr double kReduceChop = 1e-16;  // reduce_zeros' CHOP on sigma^2 (mps.hip kChop)
+// Both Gram paths (svd_gram.h gs_clusters, gram_big.hip k_gb_gs): eigenvalues of T closer than this
+// times ||T|| share a cluster and are orthogonalised against each other after the inverse iteration
+constexpr double kGramClusterGap = 1e-5;
 
 // reduce_zeros (oracle/mps.py truncation_rank: Aer's rule as the reference drives it,
 // aer_mps_backend.py:27-42) on the top KE eigenvalues lam (descending, = sigma^2) of G, each known to

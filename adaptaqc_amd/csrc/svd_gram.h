@@ -16,7 +16,7 @@
 //       Sturm count -- the minors' three-term recurrence, one dependent FMA per row -- one ballot
 //       picks the subinterval; 12 rounds)
 //   S5  inverse iteration (unpivoted LDL^T of T - lambda I, three solves) per eigenvector, Gram-
-//       Schmidt inside clusters (gaps below 1e-7 ||T||), sigma^2 = z^T T z
+//       Schmidt inside clusters (gaps below 1e-5 ||T||), sigma^2 = z^T T z
 //   S6  back-transformation V = Q Z: blocks of 16 reflectors in compact WY form on the matrix
 //       cores, V in the accumulators throughout; output W = V Sigma
 // The output follows the QR-preconditioned register Jacobi's contract (TwoSiteJob::qr = 1): work
@@ -249,30 +249,77 @@ __device__ __forceinline__ void s6_factors(int b, int C, cplx* hh, const cplx* s
   for (int m = 0; m < 4; ++m) aqc::stg(Sg + 256 + a * 16 + g + 4 * m, tq[m]);
 }
 
-// Gram-Schmidt inside clusters of the S5 vectors (zb[row * ZS + i]), one wave
-template <int ZS>
-__device__ __forceinline__ void gs_clusters(int K, int C, double* zb, const double* s_lam, double s_tn, int lane) {
-  // clusters: gaps below 1e-7 ||T|| (dstein's 1e-3 is far more conservative than three
-  // inverse-iteration steps need: at gaps above ~1e-10 the vectors come out orthogonal to
-  // 1e-14 on their own, tools/gram_svd_proto.py)
-  const double ortol = 1e-7 * s_tn;
-  int start = 0;
-  for (int i = 1; i < K; ++i) {
-    if (s_lam[i - 1] - s_lam[i] >= ortol) {
-      start = i;
-      continue;
-    }
-    for (int jj = start; jj < i; ++jj) {
-      double dp = 0.0;
-      for (int row = lane; row < C; row += 64) dp = fma(zb[row * ZS + i], zb[row * ZS + jj], dp);
-      dp = wave_sum_d(dp);
-      for (int row = lane; row < C; row += 64) zb[row * ZS + i] = fma(-dp, zb[row * ZS + jj], zb[row * ZS + i]);
-    }
+// Gram-Schmidt inside clusters of the S5 vectors (zb[row * ZS + i]), one wave.  ldd(row, i): 1 / D_row
+// of vector i's L D L^T factors, as S5 left them.
+// Clusters: gaps below kGramClusterGap ||T|| = 1e-5 ||T|| (LAPACK dstein's 1e-3 would put most of a
+// graded spectrum's small sigma^2 into one cluster), see below for the gaps above 1e-7 ||T||.  Inverse iteration alone leaves two vectors
+// orthogonal to ~eps ||T|| / gap: with 1e-7 ||T|| here, pairs at 5e-8 ... 1e-5 ||T|| came out with
+// |V^H V - I| up to 7e-12 and ||theta_dev - theta_K|| up to 1.1e-12 (tests/test_gpu_small_svd.py,
+// `pairs`; gram_big.hip's k_gb_gs went the same way).
+// A member that the projection shrinks below half of its norm was nearly in the span of the earlier
+// ones -- the shifts of an exact multiplet differ by rounding only, so two of its vectors can be the
+// same eigenvector to 1e-5 -- and what is left of it is rounding noise scaled up, in the cluster's
+// directions and outside them (an 8-fold sigma came out with |V^H V - I| = 1.8e-11 in k_chain and
+// 1e-14 in the lock-step launches, on thetas that differ in their last bits).  As dstein does, such
+// a member takes one more inverse-iteration step from the projected vector (lane 0, the factors are
+// still there), which restores the cluster's directions over everything else, and is projected
+// again; at most twice.
+template <int ZS, class LoadD>
+__device__ __forceinline__ void gs_clusters(int K, int C, double* zb, const double* s_lam, const double* s_e,
+                                            double s_tn, int lane, LoadD ldd) {
+  // Between 1e-7 ||T|| and kGramClusterGap ||T|| only a gap that is also small against the
+  // eigenvalues themselves (5% of them) joins them: the |0>-started circuits of
+  // test_fused_chain_matches_lockstep_and_oracle keep sigma^2 from 1e-5 ||T|| down to the 1e-9 floor,
+  // decades apart, and with all of those in one cluster the overlap of one of its states moved from
+  // 2.2e-10 to 2.1e-9 of the oracle's
+  const double ortol = aqc::kGramClusterGap * s_tn, ortol_any = 1e-7 * s_tn;
+  auto normalise = [&](int i) {  // returns the squared norm before
     double n2 = 0.0;
     for (int row = lane; row < C; row += 64) n2 = fma(zb[row * ZS + i], zb[row * ZS + i], n2);
     n2 = wave_sum_d(n2);
-    const double sc = 1.0 / sqrt(n2);
+    const double sc = 1.0 / sqrt(fmax(n2, 1e-300));
     for (int row = lane; row < C; row += 64) zb[row * ZS + i] *= sc;
+    return n2;
+  };
+  int start = 0;
+  for (int i = 1; i < K; ++i) {
+    const double gap = s_lam[i - 1] - s_lam[i];
+    if (gap >= ortol || (gap >= ortol_any && gap >= 0.05 * s_lam[i - 1])) {
+      start = i;
+      continue;
+    }
+    for (int again = 0;; ++again) {  // (uniform: every value below is a wave sum)
+      for (int jj = start; jj < i; ++jj) {
+        double dp = 0.0;
+        for (int row = lane; row < C; row += 64) dp = fma(zb[row * ZS + i], zb[row * ZS + jj], dp);
+        dp = wave_sum_d(dp);
+        for (int row = lane; row < C; row += 64) zb[row * ZS + i] = fma(-dp, zb[row * ZS + jj], zb[row * ZS + i]);
+      }
+      const double n2 = normalise(i);  // (the vector came in with unit norm)
+      if (n2 > 0.5 || again == 2) break;
+      // (T - lam_i I) z' = z: forward solve L y = z in place, then z' = D^-1 y - L^T z' from the bottom
+      // (S5's own recurrences).  One lane writes every row: the wave's LDS accesses complete in order,
+      // the waits keep the compiler from moving the other lanes' accesses across
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_wave_barrier();
+      if (lane == 0) {
+        double yp = 0.0;
+        for (int row = 0; row < C; ++row) {
+          const int rm = max(row - 1, 0);
+          yp = fma(-s_e[rm] * ldd(rm, i), yp, zb[row * ZS + i]);
+          zb[row * ZS + i] = yp;
+        }
+        double zn = 0.0;
+        for (int row = C - 1; row >= 0; --row) {
+          const double d = ldd(row, i);
+          zn = fma(-s_e[min(row, C - 2)] * d, zn, zb[row * ZS + i] * d);
+          zb[row * ZS + i] = zn;
+        }
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_wave_barrier();
+      normalise(i);
+    }
   }
 }
 
@@ -561,7 +608,10 @@ __device__ __noinline__ void gram_wide(const TwoSiteJob& j, cplx* hh, int C, int
     if (b < nblk) s6_factors(b, C, hh, s_tau, lane);
   }
   __syncthreads();
-  if (wave == 0) gs_clusters<128>(K, C, zb, s_lam, s_tn, lane);
+  if (wave == 0)
+    gs_clusters<128>(K, C, zb, s_lam, s_e, s_tn, lane, [&](int row, int i) {
+      return __hip_atomic_load((const gdbl_t*)(scratch + row * 128 + i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    });
   __syncthreads();
   if (tid < K) s_sig2[tid] = rayleigh<128>(tid, C, zb, s_d, s_e);
   __syncthreads();
@@ -1442,7 +1492,8 @@ int gram_svd_body(const TwoSiteJob& j) {
     s6_factors(wave - 1 - (wave >> 2), C, hh, s_tau, lane);
   }
   __syncthreads();
-  if (wave == 0) gs_clusters<64>(K, C, zb, s_lam, s_tn, lane);  // (uniform loop over wave 0)
+  if (wave == 0)  // (uniform loop over wave 0)
+    gs_clusters<64>(K, C, zb, s_lam, s_e, s_tn, lane, [&](int row, int i) { return Db[row * 64 + i]; });
   __syncthreads();
   if (tid < K) s_sig2[tid] = rayleigh<64>(tid, C, zb, s_d, s_e);
   __syncthreads();
