@@ -96,7 +96,8 @@ class SamplingSimulator:
     qubits) unless this is True; then method "matrix_product_state", and "automatic" above
     MAX_NOISY_QUBITS, run it as MPS trajectories (aqc_mps_traj_sample) under the simulator's
     truncation options.  Opt-in, because an MPS trajectory costs about three two-site SVDs per noisy
-    gate: every Kraus operator has to meet the orthogonality centre."""
+    gate: every Kraus operator has to meet the orthogonality centre.  The same flag and the same rule
+    (``_trajectory_engine``) put QiskitSamplingBackend's noisy pair tomography on the MPS engine."""
 
     name = "hip_sampling_simulator"
     METHODS = ("automatic", "statevector", "matrix_product_state")
@@ -146,6 +147,16 @@ class SamplingSimulator:
         self._last = (n, method, key, dev)
         return dev
 
+    def _trajectory_engine(self, n):
+        """The engine a noise model's trajectories of n qubits ask for: "matrix_product_state" for that
+        method and for "automatic" above MAX_NOISY_QUBITS, else "statevector".  Shots and pair
+        tomography both decide by it; whether the engine may run (``mps_trajectories``, the statevector
+        limit) is the caller's to check, each with its own message."""
+        method = self.options.method
+        if method == "matrix_product_state" or (method == "automatic" and n > self.MAX_NOISY_QUBITS):
+            return "matrix_product_state"
+        return "statevector"
+
     def _noisy_program(self, circuit, noise_model):
         """(rows, n_events, engine) of the circuit's trajectories under ``noise_model``, or None when no
         Kraus row comes of it (no model, an empty or all-identity one): the noiseless path then."""
@@ -157,8 +168,7 @@ class SamplingSimulator:
         if n_events == 0:
             return None
         n = circuit.num_qubits
-        method = self.options.method
-        if method == "matrix_product_state" or (method == "automatic" and n > self.MAX_NOISY_QUBITS):
+        if self._trajectory_engine(n) == "matrix_product_state":
             if not self.mps_trajectories:
                 raise NotImplementedError(
                     "a noise model runs as statevector trajectories (method 'statevector', or 'automatic' up to "
@@ -171,11 +181,11 @@ class SamplingSimulator:
                 "'matrix_product_state' with mps_trajectories=True")
         return rows, n_events, "statevector"
 
-    def _mps_trajectories(self, n, rows, n_events, shots, seed, run):
-        """The shots as MPS trajectories at the capacity of chi_cap_for; a capacity overflow grows the
-        learned capacity and runs the call again -- the same shots, their uniforms being counters."""
+    def _at_learned_capacity(self, n, call):
+        """``call(chi_cap=, threshold=, max_chi=)`` -- a batch of MPS trajectories of n qubits -- at the
+        capacity of chi_cap_for under the simulator's truncation options; a capacity overflow grows the
+        learned capacity and runs the call again: the same trajectories, their uniforms being counters."""
         from .._lib import AqcError
-        from ..device import mps_trajectory_sample
         from ..mps_operations import chi_cap_for, grow_capacity, is_capacity_error, learned_capacities
 
         thr = self.options.matrix_product_state_truncation_threshold
@@ -184,11 +194,17 @@ class SamplingSimulator:
         while True:
             cap = chi_cap_for(n, max_chi, 1, learned)
             try:
-                return mps_trajectory_sample(n, rows, n_events, shots, seed, run, chi_cap=cap, threshold=thr,
-                                             max_chi=max_chi)
+                return call(chi_cap=cap, threshold=thr, max_chi=max_chi)
             except AqcError as e:
                 if not (is_capacity_error(e) and grow_capacity(n, max_chi, cap, learned)):
                     raise
+
+    def _mps_trajectories(self, n, rows, n_events, shots, seed, run):
+        """The shots as MPS trajectories (aqc_mps_traj_sample) at the learned capacity."""
+        from ..device import mps_trajectory_sample
+
+        return self._at_learned_capacity(
+            n, lambda **cap: mps_trajectory_sample(n, rows, n_events, shots, seed, run, **cap))
 
     def run(self, circuit, shots=1024, seed_simulator=None, noise_model=None, **ignored):
         """``noise_model`` (adaptaqc_amd.noise.NoiseModel): every shot is then one quantum trajectory on
@@ -311,8 +327,11 @@ class QiskitSamplingBackend(AQCBackend):
     errors the model attaches to the appended ``sdg`` / ``h`` / ``measure`` folded into POVM effects
     (noise.readout_effects).  A pair's nine tables have the law of the reference's nine noisy circuits;
     tables of different pairs share trajectories and are correlated, which the per-pair fit never
-    sees.  Opt-in, because the sweep costs 9 x shots trajectories.  Statevector trajectories only (at
-    most 24 qubits); the concurrence lower bound stays noiseless-only.
+    sees.  Opt-in, because the sweep costs 9 x shots trajectories.  Statevector trajectories up to 24
+    qubits.  With a simulator built with ``mps_trajectories=True``, method "matrix_product_state", and
+    "automatic" above 24 qubits, run the trajectories on the MPS engine instead
+    (aqc_mps_traj_pair_tomo: every pair read from the trajectory's RDMs), at the simulator's learned
+    capacity as its noisy shots do.  The concurrence lower bound stays noiseless-only.
     """
 
     TOMOGRAPHY_MODES = (None, "circuits", "device")
@@ -346,8 +365,8 @@ class QiskitSamplingBackend(AQCBackend):
                                       f"honour a noise_model for {what}: {hint}")
 
     def _noisy_tomography_program(self, circuit, noise_model):
-        """(rows, n_events, effects) of the noisy device route, or None when ``noise_model`` has no
-        effective error on the circuit or on the readout (the pure-state route then)."""
+        """(rows, n_events, effects, engine) of the noisy device route, or None when ``noise_model`` has
+        no effective error on the circuit or on the readout (the pure-state route then)."""
         from ..noise import readout_effects, trajectory_program
 
         if noise_model is None:
@@ -360,13 +379,28 @@ class QiskitSamplingBackend(AQCBackend):
             return None
         sim = self.simulator
         method = sim.options.method
+        if sim._trajectory_engine(n) == "matrix_product_state" and sim.mps_trajectories:
+            return rows, n_events, readout_effects(n, noise_model), "matrix_product_state"
         if method == "matrix_product_state":
             raise NotImplementedError("trajectory_tomography runs statevector trajectories: a noise_model with "
-                                      "method 'matrix_product_state' is not supported")
+                                      "method 'matrix_product_state' is not supported unless the simulator is "
+                                      "built with mps_trajectories=True, which runs it as MPS trajectories")
         if n > sim.MAX_NOISY_QUBITS:
             raise NotImplementedError(f"trajectory_tomography runs statevector trajectories, which stop at "
-                                      f"{sim.MAX_NOISY_QUBITS} qubits (method {method!r}, {n} qubits)")
-        return rows, n_events, readout_effects(n, noise_model)
+                                      f"{sim.MAX_NOISY_QUBITS} qubits (method {method!r}, {n} qubits): use method "
+                                      "'automatic' or 'matrix_product_state' with a simulator built with "
+                                      "mps_trajectories=True")
+        return rows, n_events, readout_effects(n, noise_model), "statevector"
+
+    def _noisy_counts(self, n, noisy, pairs, shots, seed, run):
+        """The int64 [npairs, 9, 4] tables of the noisy device route on the engine ``noisy`` names."""
+        from ..device import mps_trajectory_pair_tomography, trajectory_pair_tomography
+
+        rows, n_events, effects, engine = noisy
+        if engine == "statevector":
+            return trajectory_pair_tomography(n, rows, n_events, pairs, effects, shots, seed, run)
+        return self.simulator._at_learned_capacity(
+            n, lambda **cap: mps_trajectory_pair_tomography(n, rows, n_events, pairs, effects, shots, seed, run, **cap))
 
     def _seed_and_run(self, kwargs):
         """(seed, run) of one device sweep: ``seed_simulator`` alone when given, else the
@@ -381,7 +415,7 @@ class QiskitSamplingBackend(AQCBackend):
         """(rho [npairs, 4, 4], measures [npairs] or None) of the state ``circuit`` prepares, from
         ``execute_kwargs["shots"]`` shots per Pauli setting.  ``measure``: a name of
         device.EM_METHOD_CODES.  RDM index 2 bit_hi + bit_lo with hi the pair's larger qubit."""
-        from ..device import entanglement_measures, pair_tomography, tomo_fit, trajectory_pair_tomography
+        from ..device import entanglement_measures, pair_tomography, tomo_fit
 
         self._require_tomography()
         kwargs = dict(execute_kwargs or {})
@@ -393,8 +427,7 @@ class QiskitSamplingBackend(AQCBackend):
             if not pairs:
                 return np.zeros((0, 4, 4), dtype=complex), (None if measure is None else np.zeros(0))
             seed, run = self._seed_and_run(kwargs)
-            counts = trajectory_pair_tomography(circuit.num_qubits, noisy[0], noisy[1], pairs, noisy[2],
-                                                int(kwargs.get("shots", 1024)), seed, run)
+            counts = self._noisy_counts(circuit.num_qubits, noisy, pairs, int(kwargs.get("shots", 1024)), seed, run)
             rho = tomo_fit(counts)
             return rho, (None if measure is None else entanglement_measures(rho, measure))
         if self.tomography == "device":

@@ -1117,6 +1117,14 @@ int aqc::mps_envs_batch(aqc_mps_s** hs, int ns, size_t extra_bytes, const char* 
   return AQC_OK;
 }
 
+// What aqc_mps_pair_rdms_batch lays out per state in the per-device buffer: both environment sides,
+// the chains' scratch, P and U of every site, the chains of the `na` distinct lower qubits and the
+// n x n table of 4x4 blocks (see mps_internal.h).
+size_t aqc::pair_rdm_state_bytes(int n, int cap, int na) {
+  const size_t cc = (size_t)cap * cap;
+  return (2 * (size_t)(n + 1) * cc + 4 * cc + 6 * (size_t)n * cc + 12 * (size_t)na * cc + (size_t)n * n * 16) * sizeof(cplx);
+}
+
 extern "C" {
 
 int aqc_mps_pair_rdms_batch(aqc_mps_t* hs, int ns, const int* pairs, int npairs, double* out, int out_is_device) {
@@ -1140,8 +1148,7 @@ int aqc_mps_pair_rdms_batch(aqc_mps_t* hs, int ns, const int* pairs, int npairs,
   }
   const int na = (int)alist.size();
   const size_t cc = (size_t)cap * cap;
-  const size_t per_state =
-      (2 * (size_t)(n + 1) * cc + 4 * cc + 6 * (size_t)n * cc + 12 * (size_t)na * cc + (size_t)n * n * 16) * sizeof(cplx);
+  const size_t per_state = aqc::pair_rdm_state_bytes(n, cap, na);
   const size_t jb = aqc::up256(ns * sizeof(RdmJob));
   const size_t pb = aqc::up256(2 * npairs * sizeof(int) + na * sizeof(int));
   const size_t ob = out_is_device ? 0 : (size_t)ns * npairs * 16 * sizeof(cplx);

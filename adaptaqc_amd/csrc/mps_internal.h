@@ -452,11 +452,12 @@ struct Scheduler {
 
 // What the Kraus / measurement rows of a batch of trajectories share (mps_traj.hip): state s of the
 // lists handed to run_waves carries shot shot0 + s.  Row slots: Kraus event e -> e, the measurement of
-// qubit q -> nev + q, out of nper = nev + n per shot.
+// qubit q -> nev + q, out of nper = nev + n per shot (aqc_mps_traj_pair_tomo has no measurement rows:
+// nper = nev + npairs, pair j's draw in slot nev + j).
 struct TrajCtx {
   uint64_t seed, run;
   const double* u;   // device: null, or [shot][nper] uniforms replacing sample_uniform(seed, run, shot, slot)
-  uint64_t* out;     // device: [shot][words] outcome words, zeroed by the caller
+  uint64_t* out;     // device: [shot][words] outcome words, zeroed by the caller (null without measurement rows)
   uint8_t* choices;  // device: null, or [shot][nev]
   int shot0, nev, nper, words;
 };
@@ -507,6 +508,9 @@ int mps_right_envs(aqc_mps_s* h, size_t extra_bytes, const cplx** renv, void** e
 // names the launches for aqc_timing_query; the rest as above (*extra is 16-byte aligned).
 int mps_envs_batch(aqc_mps_s** hs, int ns, size_t extra_bytes, const char* family, const cplx** lenv,
                    size_t* state_stride, void** extra, hipStream_t* stream);
+// Bytes of that buffer aqc_mps_pair_rdms_batch takes per state of n qubits at capacity cap, for pairs
+// with `na` distinct lower qubits (a caller that budgets device memory sizes its batches by it).
+size_t pair_rdm_state_bytes(int n, int cap, int na);
 }
 
 struct aqc_mps_s {

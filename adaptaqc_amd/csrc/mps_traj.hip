@@ -27,12 +27,21 @@
 // the four waves in index order through the LDS; no atomics: two calls return the same bits).
 // p_k = Re Tr(K_k^dag K_k rho) and the choice follow aqc_sv_traj_sample's rule, a measurement row
 // aqc_mps_sample's bit = [u (p0 + p1) >= p0].  Pass 2: Gamma^s <- sum_s' K_k[s][s'] / sqrt(p_k) Gamma^s'.
+//
+// Noisy pair tomography (aqc_mps_traj_pair_tomo): the same schedule without the measurement sweep
+// (gate rows, Kraus rows at the centre, the flush and the sort), 9 nshots trajectories, trajectory t
+// serving Pauli setting t % 9 of every pair.  A batch's states are then read out by the all-pair RDM
+// sweep that assumes no canonical form (aqc_mps_pair_rdms_batch, ent.hip, into device memory), and
+// k_mps_traj_pair_draw -- one thread per (state, pair) -- forms the four outcome probabilities from
+// the RDM and the two qubits' POVM effects with the arithmetic of k_sv_traj's pair ending
+// (pair_draw.h), draws one outcome and adds it to the integer count table on the device.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
 #include "mps_internal.h"
+#include "pair_draw.h"
 #include "sample_rng.h"
 
 using aqc::cplx;
@@ -45,11 +54,15 @@ namespace {
 constexpr int kKT = 256;
 constexpr int kMaxShots = 1 << 30;
 constexpr int kMaxBatch = 256;
+constexpr int kMaxPairs = 4096;
+constexpr int kDT = 256;  // threads of k_mps_traj_pair_draw
+constexpr int kReadoutStates = 16;  // states per RDM sweep of the pair readout
 // device memory the batch's MPS handles may take together (each: the Gammas, n 2 cap^2 complex, and
 // one two-site workspace per concurrent update of the widest wave)
 constexpr size_t kBatchBudgetBytes = (size_t)4 << 30;
 constexpr int kChunkRows = 64;  // schedule rows per run_waves call (bounds the job staging)
 int g_forced_batch = 0;
+int g_forced_readout = 0;  // aqc_mps_traj_set_readout_batch: states per RDM sweep of the pair readout
 
 __device__ __forceinline__ double wave_sum(double v) {
   for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d, 64);
@@ -150,6 +163,50 @@ __global__ __launch_bounds__(kKT) void k_mps_kraus1(const KrausJob* __restrict__
   }
 }
 
+// The pair readout of nr states of a batch: state s of the sweep is trajectory traj0 + s, state
+// local0 + s of the batch (the batch's uniforms and outcome bytes are indexed by that).
+struct PairDrawJob {
+  const cplx* rdm;             // [nr][npairs][16], row-major 4x4, index 2 bit_hi + bit_lo
+  const int* pairs;            // 2 npairs
+  const double* effects;       // [n][3][2][4]: (E00, E11, Re E01, Im E01)
+  const double* u;             // null, or the batch's [state][nper]
+  unsigned long long* counts;  // [npairs][9][4]
+  uint8_t* outcomes;           // null, or the batch's [state][npairs]
+  uint64_t seed, run;
+  int traj0, local0, nr, npairs, nev, nper;
+};
+
+// One thread per (state, pair): no sum crosses a thread, so the order is fixed; the table takes
+// integer atomics only.
+__global__ __launch_bounds__(kDT) void k_mps_traj_pair_draw(const PairDrawJob j) {
+  const int e = blockIdx.x * kDT + threadIdx.x;
+  if (e >= j.nr * j.npairs) return;
+  const int s = e / j.npairs, pj = e - s * j.npairs;
+  const int t = j.traj0 + s, local = j.local0 + s, s9 = t % 9;
+  const int qa = j.pairs[2 * pj], qb = j.pairs[2 * pj + 1];
+  const int lo = qa < qb ? qa : qb, hi = qa < qb ? qb : qa;
+  const cplx* rho = j.rdm + (size_t)e * 16;
+  double d[4], ox[6], oy[6];  // rho_ss; rho_st, s < t
+  int c = 0;
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    d[a] = aqc::ldg(rho + 5 * a).x;
+#pragma unroll
+    for (int b = a + 1; b < 4; ++b, ++c) {
+      const cplx z = aqc::ldg(rho + 4 * a + b);
+      ox[c] = z.x;
+      oy[c] = z.y;
+    }
+  }
+  const double* eh = j.effects + (size_t)((hi * 3 + s9 / 3) * 2) * 4;
+  const double* el = j.effects + (size_t)((lo * 3 + s9 % 3) * 2) * 4;
+  const double uu = j.u ? aqc::ldg(j.u + (size_t)local * j.nper + j.nev + pj)
+                        : aqc::sample_uniform(j.seed, j.run, (uint64_t)t, (uint32_t)(j.nev + pj));
+  const int k = aqc::pair_outcome(eh, el, d, ox, oy, uu);
+  if (j.outcomes) j.outcomes[(size_t)local * j.npairs + pj] = (uint8_t)k;
+  atomicAdd(j.counts + ((size_t)pj * 9 + s9) * 4 + k, 1ULL);
+}
+
 // ---- the site-level schedule -----------------------------------------------------------------
 enum { tGate = 0, tSwap = 1, tMove = 2, tOne = 3, tKraus = 4, tMeas = 5 };
 
@@ -159,8 +216,10 @@ struct TrajSched {
   int nev = 0;
 };
 
+thread_local const char* t_entry = "aqc_mps_traj_sample";  // the entry point named in error messages
+
 int fail(const std::string& msg) {
-  aqc::set_error("aqc_mps_traj_sample: " + msg);
+  aqc::set_error(std::string(t_entry) + ": " + msg);
   return AQC_ERR_ARG;
 }
 
@@ -255,7 +314,9 @@ struct Planner {
     a = b = p;
   }
 
-  void run(const aqc_op_t* prog, int nprog) {
+  // measure: the sweep of measurement rows behind the sort (the sampler's ending; the pair readout
+  // stops at the sorted state)
+  void run(const aqc_op_t* prog, int nprog, bool measure) {
     for (int i = 0; i < nprog; ++i) {
       const aqc_op_t& op = prog[i];
       if (op.flags == AQC_OP_KRAUS1) {
@@ -278,16 +339,17 @@ struct Planner {
     drain(false);
     sc.sort();
     drain(false);
+    if (!measure) return;
     cplx proj[8];
     for (int e = 0; e < 8; ++e) proj[e] = aqc::hc(e == 0 || e == 7 ? 1 : 0, 0);
     for (int q = 0; q < n; ++q) row(q, 2, proj, q, 1);
   }
 };
 
-int build_schedule(int n, const aqc_op_t* prog, int nprog, TrajSched& s) {
+int build_schedule(int n, const aqc_op_t* prog, int nprog, TrajSched& s, bool measure = true) {
   if (int rc = validate(n, prog, nprog)) return rc;
   Planner pl(n, s);
-  pl.run(prog, nprog);
+  pl.run(prog, nprog, measure);
   return AQC_OK;
 }
 
@@ -319,33 +381,41 @@ struct Handles {
   ~Handles() {
     for (aqc_mps_t x : h) aqc_mps_destroy(x);
   }
+  int create(int count, int n, int chi_cap, double threshold, int max_chi) {
+    h.reserve(count);
+    for (int s = 0; s < count; ++s) {
+      aqc_mps_t x = nullptr;
+      if (int rc = aqc_mps_create(n, chi_cap, threshold, max_chi, &x)) return rc;
+      h.push_back(x);
+    }
+    return AQC_OK;
+  }
 };
 
-}  // namespace
-
-int aqc::launch_kraus(const KrausJob* jobs, int nj, const TrajCtx& ctx, hipStream_t st) {
-  // each job: the site's two Gammas read twice and written once, the lambdas
-  KernelTimer::begin(st, "mps_kraus1", 0.0, 0.0);
-  hipLaunchKernelGGL(k_mps_kraus1, dim3(nj), dim3(kKT), 0, st, jobs, ctx);
-  KernelTimer::end(st);
-  AQC_CHECK_LAUNCH();
-  return AQC_OK;
+// device bytes of one trajectory's handle while the schedule runs: the Gammas, and one two-site
+// workspace per concurrent update of the widest wave of a chunk
+size_t evolve_state_bytes(const TrajSched& sch, int n, size_t cap) {
+  const size_t nrows = sch.ops.size();
+  int width = 1;
+  for (size_t r0 = 0; r0 < nrows; r0 += kChunkRows)
+    width = std::max(width, max_width(sch.ops.data() + r0, std::min<size_t>(kChunkRows, nrows - r0), n));
+  return ((size_t)n * 2 * cap * cap + (size_t)width * (4 * cap * cap + aqc::work_elems(cap))) * sizeof(cplx);
 }
 
-extern "C" {
-
-int aqc_mps_traj_set_batch(int batch) {
-  AQC_REQUIRE(batch >= 0 && batch <= 4096, "aqc_mps_traj_set_batch: 0 (default) or 1 .. 4096");
-  g_forced_batch = batch;
-  return AQC_OK;
+// The schedule's rows on nb states (state s carrying shot ctx.shot0 + s), chunk by chunk; then waits
+// for the batch and reads its flags: a capacity overflow ends the call.
+int run_rows(const TrajSched& sch, aqc_mps_t* hs, int nb, const TrajCtx& ctx, std::vector<std::vector<DevOp>>& lists) {
+  const size_t nrows = sch.ops.size();
+  for (size_t r0 = 0; r0 < nrows; r0 += kChunkRows) {
+    const size_t r1 = std::min(nrows, r0 + kChunkRows);
+    lists.assign(nb, std::vector<DevOp>(sch.ops.begin() + r0, sch.ops.begin() + r1));
+    if (int rc = aqc::run_waves(hs, nb, lists, &ctx)) return rc;
+  }
+  return aqc_mps_check_batch(hs, nb);
 }
 
-int aqc_mps_traj_plan(int n, const aqc_op_t* prog, int nprog, int* counts, aqc_op_t* sched, int sched_cap) {
-  AQC_REQUIRE(counts && nprog >= 0 && (prog || nprog == 0) && sched_cap >= 0 && (sched || sched_cap == 0),
-              "aqc_mps_traj_plan: bad argument");
-  AQC_REQUIRE(n >= 1 && n <= 4096, "aqc_mps_traj_plan: n must be in 1 .. 4096");
-  TrajSched s;
-  if (int rc = build_schedule(n, prog, nprog, s)) return rc;
+// aqc_mps_traj_plan's output of a schedule
+void write_plan(const TrajSched& s, int* counts, aqc_op_t* sched, int sched_cap) {
   for (int c = 0; c < 7; ++c) counts[c] = 0;
   for (uint8_t t : s.tag) counts[t] += 1;
   counts[6] = (int)s.ops.size();
@@ -369,11 +439,56 @@ int aqc_mps_traj_plan(int n, const aqc_op_t* prog, int nprog, int* counts, aqc_o
       std::memcpy(o.m, d.m, 4 * (size_t)d.nk * sizeof(cplx));
     }
   }
+}
+
+int plan(const char* entry, bool measure, int n, const aqc_op_t* prog, int nprog, int* counts, aqc_op_t* sched,
+         int sched_cap) {
+  t_entry = entry;
+  if (!(counts && nprog >= 0 && (prog || nprog == 0) && sched_cap >= 0 && (sched || sched_cap == 0)))
+    return fail("bad argument");
+  if (!(n >= 1 && n <= 4096)) return fail("n must be in 1 .. 4096");
+  TrajSched s;
+  if (int rc = build_schedule(n, prog, nprog, s, measure)) return rc;
+  write_plan(s, counts, sched, sched_cap);
   return AQC_OK;
+}
+
+}  // namespace
+
+int aqc::launch_kraus(const KrausJob* jobs, int nj, const TrajCtx& ctx, hipStream_t st) {
+  // each job: the site's two Gammas read twice and written once, the lambdas
+  KernelTimer::begin(st, "mps_kraus1", 0.0, 0.0);
+  hipLaunchKernelGGL(k_mps_kraus1, dim3(nj), dim3(kKT), 0, st, jobs, ctx);
+  KernelTimer::end(st);
+  AQC_CHECK_LAUNCH();
+  return AQC_OK;
+}
+
+extern "C" {
+
+int aqc_mps_traj_set_batch(int batch) {
+  AQC_REQUIRE(batch >= 0 && batch <= 4096, "aqc_mps_traj_set_batch: 0 (default) or 1 .. 4096");
+  g_forced_batch = batch;
+  return AQC_OK;
+}
+
+int aqc_mps_traj_set_readout_batch(int batch) {
+  AQC_REQUIRE(batch >= 0 && batch <= 4096, "aqc_mps_traj_set_readout_batch: 0 (default) or 1 .. 4096");
+  g_forced_readout = batch;
+  return AQC_OK;
+}
+
+int aqc_mps_traj_plan(int n, const aqc_op_t* prog, int nprog, int* counts, aqc_op_t* sched, int sched_cap) {
+  return plan("aqc_mps_traj_plan", true, n, prog, nprog, counts, sched, sched_cap);
+}
+
+int aqc_mps_traj_tomo_plan(int n, const aqc_op_t* prog, int nprog, int* counts, aqc_op_t* sched, int sched_cap) {
+  return plan("aqc_mps_traj_tomo_plan", false, n, prog, nprog, counts, sched, sched_cap);
 }
 
 int aqc_mps_traj_sample(int n, int chi_cap, double threshold, int max_chi, const aqc_op_t* prog, int nprog, int nshots,
                         uint64_t seed, uint64_t run, const double* u, uint64_t* out, uint8_t* choices) {
+  t_entry = "aqc_mps_traj_sample";
   AQC_REQUIRE(out && nprog >= 0 && (prog || nprog == 0), "aqc_mps_traj_sample: null argument");
   AQC_REQUIRE(n >= 1 && n <= 4096, "aqc_mps_traj_sample: n must be in 1 .. 4096");
   AQC_REQUIRE(chi_cap >= 1 && chi_cap <= aqc::kMaxCap, "aqc_mps_traj_sample: chi_cap must be in [1, 1024]");
@@ -385,22 +500,12 @@ int aqc_mps_traj_sample(int n, int chi_cap, double threshold, int max_chi, const
     for (size_t e = 0, nu = (size_t)nshots * nper; e < nu; ++e)
       if (!(u[e] >= 0.0 && u[e] < 1.0)) return fail("u must lie in [0, 1)");
   const bool want_choices = choices && nev > 0;
-  const size_t nrows = sch.ops.size();
   // the batch: B trajectories as B handles
-  int width = 1;
-  for (size_t r0 = 0; r0 < nrows; r0 += kChunkRows)
-    width = std::max(width, max_width(sch.ops.data() + r0, std::min<size_t>(kChunkRows, nrows - r0), n));
-  const size_t cap = chi_cap;
-  const size_t per_state = ((size_t)n * 2 * cap * cap + (size_t)width * (4 * cap * cap + aqc::work_elems(cap))) * sizeof(cplx);
+  const size_t per_state = evolve_state_bytes(sch, n, chi_cap);
   int B = (int)std::min<size_t>({(size_t)nshots, (size_t)kMaxBatch, std::max<size_t>(1, kBatchBudgetBytes / per_state)});
   if (g_forced_batch > 0) B = std::min(nshots, g_forced_batch);
   Handles hs;
-  hs.h.reserve(B);
-  for (int s = 0; s < B; ++s) {
-    aqc_mps_t h = nullptr;
-    if (int rc = aqc_mps_create(n, chi_cap, threshold, max_chi, &h)) return rc;
-    hs.h.push_back(h);
-  }
+  if (int rc = hs.create(B, n, chi_cap, threshold, max_chi)) return rc;
   hipStream_t st = aqc::mps_stream();
   const size_t ub = u ? up256((size_t)B * nper * sizeof(double)) : 0;
   const size_t ob = up256((size_t)B * words * sizeof(uint64_t));
@@ -429,19 +534,126 @@ int aqc_mps_traj_sample(int n, int chi_cap, double threshold, int max_chi, const
     if (u)
       AQC_HIP_CHECK(hipMemcpyAsync(scr.dev, u + (size_t)shot0 * nper, (size_t)nb * nper * sizeof(double),
                                    hipMemcpyHostToDevice, st));
-    for (size_t r0 = 0; r0 < nrows; r0 += kChunkRows) {
-      const size_t r1 = std::min(nrows, r0 + kChunkRows);
-      lists.assign(nb, std::vector<DevOp>(sch.ops.begin() + r0, sch.ops.begin() + r1));
-      if (int rc = aqc::run_waves(hs.h.data(), nb, lists, &ctx)) return rc;
-    }
-    // waits for the batch and reads its flags: a capacity overflow ends the call
-    if (int rc = aqc_mps_check_batch(hs.h.data(), nb)) return rc;
+    if (int rc = run_rows(sch, hs.h.data(), nb, ctx, lists)) return rc;
     AQC_HIP_CHECK(hipMemcpyAsync(out + (size_t)shot0 * words, ctx.out, (size_t)nb * words * sizeof(uint64_t),
                                  hipMemcpyDeviceToHost, st));
     if (want_choices)
       AQC_HIP_CHECK(hipMemcpyAsync(choices + (size_t)shot0 * nev, ctx.choices, (size_t)nb * nev, hipMemcpyDeviceToHost, st));
     AQC_HIP_CHECK(hipStreamSynchronize(st));
   }
+  return AQC_OK;
+}
+
+int aqc_mps_traj_pair_tomo(int n, int chi_cap, double threshold, int max_chi, const aqc_op_t* prog, int nprog,
+                           const int* pairs, int npairs, const double* effects, int nshots, uint64_t seed, uint64_t run,
+                           const double* u, int64_t* counts, uint8_t* outcomes) {
+  t_entry = "aqc_mps_traj_pair_tomo";
+  AQC_REQUIRE(counts && pairs && effects && nprog >= 0 && (prog || nprog == 0), "aqc_mps_traj_pair_tomo: null argument");
+  AQC_REQUIRE(n >= 2 && n <= 4096, "aqc_mps_traj_pair_tomo: n must be in 2 .. 4096");
+  AQC_REQUIRE(chi_cap >= 1 && chi_cap <= aqc::kMaxCap, "aqc_mps_traj_pair_tomo: chi_cap must be in [1, 1024]");
+  AQC_REQUIRE(npairs >= 1 && npairs <= kMaxPairs, "aqc_mps_traj_pair_tomo: npairs must be in 1 .. 4096");
+  AQC_REQUIRE(nshots >= 1 && nshots <= kMaxShots / 9, "aqc_mps_traj_pair_tomo: 9 nshots must be in 9 .. 2^30");
+  int na = 0;  // distinct lower qubits: what the RDM sweep's workspace grows with
+  {
+    std::vector<char> lower(n, 0);
+    for (int p = 0; p < npairs; ++p) {
+      const int a = pairs[2 * p], b = pairs[2 * p + 1];
+      if (a < 0 || a >= n || b < 0 || b >= n || a == b) return fail("a pair needs two different qubits in 0 .. n-1");
+      na += !lower[std::min(a, b)];
+      lower[std::min(a, b)] = 1;
+    }
+  }
+  if (int rc = aqc::check_effects(n, effects, t_entry)) return rc;
+  TrajSched sch;
+  if (int rc = build_schedule(n, prog, nprog, sch, false)) return rc;
+  const int ntraj = 9 * nshots;
+  const int nev = sch.nev, nper = nev + npairs;
+  if (u)
+    for (size_t e = 0, nu = (size_t)ntraj * nper; e < nu; ++e)
+      if (!(u[e] >= 0.0 && u[e] < 1.0)) return fail("u must lie in [0, 1)");
+  // The batch: B trajectories run the schedule together as B handles and are read out R at a time,
+  // B evolve + R readout within the budget (readout: the RDM sweep's workspace of one state and its
+  // npairs 4x4 blocks).  A wave of the schedule holds one update per state, so the run time goes with
+  // the number of batches; the sweep has a workgroup per (state, chain) and fills the chip with few
+  // states: R stays small, at most half the budget, and B takes the rest.
+  const size_t evolve = evolve_state_bytes(sch, n, chi_cap);
+  const size_t readout = aqc::pair_rdm_state_bytes(n, chi_cap, na) + (size_t)npairs * 16 * sizeof(cplx);
+  int R = (int)std::max<size_t>(1, std::min<size_t>({(size_t)kReadoutStates, (size_t)ntraj, kBatchBudgetBytes / 2 / readout}));
+  const size_t left = kBatchBudgetBytes - std::min(kBatchBudgetBytes, (size_t)R * readout);
+  int B = (int)std::min<size_t>({(size_t)ntraj, (size_t)kMaxBatch, std::max<size_t>(1, left / evolve)});
+  if (g_forced_batch > 0) {  // what a forced batch leaves of the budget
+    B = std::min(ntraj, g_forced_batch);
+    const size_t held = std::min(kBatchBudgetBytes, (size_t)B * evolve);
+    R = (int)std::max<size_t>(1, std::min<size_t>((size_t)R, (kBatchBudgetBytes - held) / readout));
+  }
+  R = std::min(R, B);
+  if (g_forced_readout > 0) R = std::min(B, g_forced_readout);
+  Handles hs;
+  if (int rc = hs.create(B, n, chi_cap, threshold, max_chi)) return rc;
+  hipStream_t st = aqc::mps_stream();
+  const size_t ub = u ? up256((size_t)B * nper * sizeof(double)) : 0;
+  const size_t qb = up256((size_t)npairs * 2 * sizeof(int));
+  const size_t eb = up256((size_t)n * 24 * sizeof(double));
+  const size_t tb = up256((size_t)npairs * 36 * sizeof(int64_t));
+  const size_t ob = outcomes ? up256((size_t)B * npairs) : 0;
+  const size_t rb = up256((size_t)R * npairs * 16 * sizeof(cplx));
+  AQC_HIP_CHECK(hipStreamSynchronize(st));  // (the scratch may be regrown)
+  aqc::DevScratch& scr = g_scr.here();
+  if (int rc = scr.ensure(ub + qb + eb + tb + ob + rb)) return rc;
+  char* buf = scr.dev;
+  TrajCtx ctx;
+  std::memset(&ctx, 0, sizeof(ctx));
+  ctx.seed = seed;
+  ctx.run = run;
+  ctx.u = u ? (const double*)buf : nullptr;
+  ctx.nev = nev;
+  ctx.nper = nper;
+  PairDrawJob dj;
+  std::memset(&dj, 0, sizeof(dj));
+  dj.u = ctx.u;
+  dj.pairs = (const int*)(buf + ub);
+  dj.effects = (const double*)(buf + ub + qb);
+  dj.counts = (unsigned long long*)(buf + ub + qb + eb);
+  dj.outcomes = outcomes ? (uint8_t*)(buf + ub + qb + eb + tb) : nullptr;
+  dj.rdm = (const cplx*)(buf + ub + qb + eb + tb + ob);
+  dj.seed = seed;
+  dj.run = run;
+  dj.npairs = npairs;
+  dj.nev = nev;
+  dj.nper = nper;
+  AQC_HIP_CHECK(hipMemcpyAsync((void*)dj.pairs, pairs, (size_t)npairs * 2 * sizeof(int), hipMemcpyHostToDevice, st));
+  AQC_HIP_CHECK(hipMemcpyAsync((void*)dj.effects, effects, (size_t)n * 24 * sizeof(double), hipMemcpyHostToDevice, st));
+  AQC_HIP_CHECK(hipMemsetAsync(dj.counts, 0, (size_t)npairs * 36 * sizeof(int64_t), st));
+  std::vector<std::vector<DevOp>> lists;
+  for (int t0 = 0; t0 < ntraj; t0 += B) {
+    const int nb = std::min(B, ntraj - t0);
+    ctx.shot0 = t0;
+    if (t0 > 0)
+      for (int s = 0; s < nb; ++s)
+        if (int rc = aqc::mps_reset_zero(hs.h[s])) return rc;
+    if (u)
+      AQC_HIP_CHECK(hipMemcpyAsync(buf, u + (size_t)t0 * nper, (size_t)nb * nper * sizeof(double), hipMemcpyHostToDevice, st));
+    if (int rc = run_rows(sch, hs.h.data(), nb, ctx, lists)) return rc;
+    for (int r0 = 0; r0 < nb; r0 += R) {
+      const int nr = std::min(R, nb - r0);
+      // every pair's RDM of the sweep's states, by full contraction (a Kraus row has broken Vidal form)
+      if (int rc = aqc_mps_pair_rdms_batch(hs.h.data() + r0, nr, pairs, npairs, (double*)dj.rdm, 1)) return rc;
+      dj.traj0 = t0 + r0;
+      dj.local0 = r0;
+      dj.nr = nr;
+      // each thread: 16 complex of RDM and two effects read, one byte and one count written
+      aqc::KernelTimer::begin(st, "mps_traj_pair_draw", (double)nr * npairs * (16.0 * 16 + 64 + 9), 0.0);
+      hipLaunchKernelGGL(k_mps_traj_pair_draw, dim3((nr * npairs + kDT - 1) / kDT), dim3(kDT), 0, st, dj);
+      aqc::KernelTimer::end(st);
+      AQC_CHECK_LAUNCH();
+    }
+    if (outcomes)
+      AQC_HIP_CHECK(hipMemcpyAsync(outcomes + (size_t)t0 * npairs, dj.outcomes, (size_t)nb * npairs, hipMemcpyDeviceToHost, st));
+    AQC_HIP_CHECK(hipStreamSynchronize(st));  // the next batch overwrites the uniforms and the outcome bytes
+  }
+  // the table accumulated on the device across the batches
+  AQC_HIP_CHECK(hipMemcpyAsync(counts, dj.counts, (size_t)npairs * 36 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  AQC_HIP_CHECK(hipStreamSynchronize(st));
   return AQC_OK;
 }
 

@@ -40,6 +40,7 @@
 #include <vector>
 
 #include "aqc_internal.h"
+#include "pair_draw.h"
 #include "sample_rng.h"
 
 using aqc::cplx;
@@ -118,12 +119,6 @@ __device__ __forceinline__ double wave_scan(double v, int lane) {
     if (lane >= d) v += t;
   }
   return v;
-}
-
-// entry (r, c) of the Hermitian 2x2 effect e = (E00, E11, Re E01, Im E01)
-__device__ __forceinline__ cplx effect_entry(const double* e, int r, int c) {
-  if (r == c) return aqc::cmk(e[r], 0.0);
-  return aqc::cmk(e[2], r < c ? e[3] : -e[3]);
 }
 
 template <int MODE, int END>
@@ -289,38 +284,9 @@ __global__ __launch_bounds__(kMaxThreads) void k_sv_traj(const TrajJob j) {
         if (lane == 0) {
           const double* eh = j.effects + (size_t)((hi * 3 + s9 / 3) * 2) * 4;
           const double* el = j.effects + (size_t)((lo * 3 + s9 % 3) * 2) * 4;
-          double pk[4], P = 0.0;
-#pragma unroll
-          for (int o = 0; o < 4; ++o) {
-            const double* A = eh + 4 * (o >> 1);
-            const double* B = el + 4 * (o & 1);
-            // Tr(E rho) = sum_s E_ss rho_ss + 2 Re sum_{s<t} E_st conj(rho_st), E = A (x) B
-            double acc = 0.0;
-            int c = 0;
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-              acc += A[s >> 1] * B[s & 1] * d[s];
-#pragma unroll
-              for (int t = s + 1; t < 4; ++t, ++c) {
-                const cplx e = aqc::cmul(effect_entry(A, s >> 1, t >> 1), effect_entry(B, s & 1, t & 1));
-                acc += 2.0 * (e.x * ox[c] + e.y * oy[c]);
-              }
-            }
-            pk[o] = fmax(0.0, acc);
-            P += pk[o];
-          }
           const double uu = j.u ? j.u[(size_t)shot * j.ustride + nev + pj]
                                 : aqc::sample_uniform(j.seed, j.run, (uint64_t)shot, (uint32_t)(nev + pj));
-          const double target = uu * P;
-          int k = -1, lastnz = 0;
-          double c = 0.0;
-#pragma unroll
-          for (int o = 0; o < 4; ++o) {
-            c += pk[o];
-            if (pk[o] > 0.0) lastnz = o;
-            if (k < 0 && c > target) k = o;
-          }
-          if (k < 0) k = lastnz;
+          const int k = aqc::pair_outcome(eh, el, d, ox, oy, uu);
           if (j.outcomes) j.outcomes[(size_t)shot * j.npairs + pj] = (uint8_t)k;
           atomicAdd(j.counts + ((size_t)pj * 9 + s9) * 4 + k, 1ULL);
         }
@@ -463,24 +429,6 @@ int launch(const TrajJob& j, int grid, int threads, size_t dyn) {
   return AQC_OK;
 }
 
-// the Hermitian 2x2 effects [n][3][2][4]: finite, E0 + E1 = I within 1e-9, each PSD within 1e-12
-int check_effects(int n, const double* effects) {
-  for (int qb = 0; qb < n * 3; ++qb) {
-    const double* e0 = effects + (size_t)qb * 8;
-    const double* e1 = e0 + 4;
-    for (int c = 0; c < 8; ++c)
-      if (!std::isfinite(e0[c])) return fail("an effect is not finite");
-    if (std::fabs(e0[0] + e1[0] - 1.0) > 1e-9 || std::fabs(e0[1] + e1[1] - 1.0) > 1e-9 ||
-        std::fabs(e0[2] + e1[2]) > 1e-9 || std::fabs(e0[3] + e1[3]) > 1e-9)
-      return fail("the two effects of a qubit and basis do not sum to the identity");
-    for (const double* e : {e0, e1}) {
-      const double half_gap = std::hypot(0.5 * (e[0] - e[1]), std::hypot(e[2], e[3]));
-      if (0.5 * (e[0] + e[1]) - half_gap < -1e-12) return fail("an effect is not positive semidefinite");
-    }
-  }
-  return AQC_OK;
-}
-
 }  // namespace
 
 extern "C" int aqc_sv_traj_sample(int n, const aqc_op_t* prog, int nprog, int nshots, uint64_t seed, uint64_t run,
@@ -554,7 +502,7 @@ extern "C" int aqc_sv_traj_pair_tomo(int n, const aqc_op_t* prog, int nprog, con
     const int a = pairs[2 * p], b = pairs[2 * p + 1];
     if (a < 0 || a >= n || b < 0 || b >= n || a == b) return fail("a pair needs two different qubits in 0 .. n-1");
   }
-  if (int rc = check_effects(n, effects)) return rc;
+  if (int rc = aqc::check_effects(n, effects, t_entry)) return rc;
   std::vector<TrajRow> rows;
   int nev = 0;
   if (int rc = build_rows(n, prog, nprog, rows, &nev)) return rc;

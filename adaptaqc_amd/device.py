@@ -346,25 +346,57 @@ def mps_trajectory_sample(n, rows, n_events, shots, seed, run=0, u=None, return_
     return (out, choices) if return_choices else out
 
 
+def mps_trajectory_pair_tomography(n, rows, n_events, pairs, effects, shots, seed, run=0, u=None, return_outcomes=False,
+                                   chi_cap=64, threshold=1e-16, max_chi=None):
+    """``trajectory_pair_tomography`` on the MPS engine (aqc_mps_traj_pair_tomo): the same arguments, the
+    same int64 [npairs, 9, 4] counts and, with ``return_outcomes``, uint8 [9 shots, npairs] outcomes.
+    Every one of the 9 ``shots`` trajectories is an MPS of capacity ``chi_cap`` truncated by
+    (``threshold``, ``max_chi``), run through ``mps_trajectory_sample``'s schedule without its
+    measurement sweep and read out pair by pair from its RDMs; one that outgrows the capacity raises
+    the capacity AqcError."""
+    n, shots, n_events = int(n), int(shots), int(n_events)
+    rows = np.ascontiguousarray(rows, dtype=_lib.OP_DTYPE)
+    if int(np.count_nonzero(rows["flags"] == _lib.OP_KRAUS1)) != n_events:
+        raise ValueError("mps_trajectory_pair_tomography: n_events does not match the program's Kraus rows")
+    pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+    npairs = len(pr)
+    eff = np.ascontiguousarray(effects, dtype=np.float64)
+    if eff.shape != (n, 3, 2, 4):
+        raise ValueError(f"mps_trajectory_pair_tomography: effects must have shape {(n, 3, 2, 4)}")
+    ntraj = 9 * max(shots, 0)
+    up = _uniforms_arg(u, (ntraj, n_events + npairs))
+    counts = np.zeros((npairs, 9, 4), dtype=np.int64)
+    outcomes = np.zeros((ntraj, npairs), dtype=np.uint8) if return_outcomes else None
+    _lib.check(_lib.lib().aqc_mps_traj_pair_tomo(n, int(chi_cap), float(threshold), int(max_chi or 0),
+                                                 _lib.ptr(rows) if len(rows) else None, len(rows),
+                                                 _lib.ptr(pr) if npairs else None, npairs, _lib.ptr(eff), shots,
+                                                 _u64(seed), _u64(run), _lib.ptr(up), _lib.ptr(counts),
+                                                 _lib.ptr(outcomes) if return_outcomes and npairs else None))
+    return (counts, outcomes) if return_outcomes else counts
+
+
 MPS_TRAJECTORY_COUNTS = ("gate_updates", "swap_updates", "centre_moves", "one_site_rows", "kraus_rows",
                          "measure_rows", "rows")
 
 
-def mps_trajectory_plan(n, rows, return_schedule=False):
+def mps_trajectory_plan(n, rows, return_schedule=False, measure=True):
     """The site-level schedule every shot of ``mps_trajectory_sample`` runs (aqc_mps_traj_plan; no GPU):
     a dict of the row counts named in MPS_TRAJECTORY_COUNTS (a two-site update is a gate, swap or
     centre-move row), and with ``return_schedule`` also the rows themselves as an OP_DTYPE array
     (``q0`` the site; flags 0 unitary, ``flags & 0xff == OP_KRAUS1`` a Kraus row with its event index
-    in ``flags >> 8``, OP_MEASURE1 the measurement of qubit ``q1``; see include/aqc_hip.h)."""
+    in ``flags >> 8``, OP_MEASURE1 the measurement of qubit ``q1``; see include/aqc_hip.h).
+    ``measure=False``: the schedule of ``mps_trajectory_pair_tomography`` (aqc_mps_traj_tomo_plan), which
+    ends with the sort, before the measurement sweep."""
     rows = np.ascontiguousarray(rows, dtype=_lib.OP_DTYPE)
     counts = np.zeros(7, dtype=np.int32)
     prog = _lib.ptr(rows) if len(rows) else None
-    _lib.check(_lib.load().aqc_mps_traj_plan(int(n), prog, len(rows), _lib.ptr(counts), None, 0))
+    entry = _lib.load().aqc_mps_traj_plan if measure else _lib.load().aqc_mps_traj_tomo_plan
+    _lib.check(entry(int(n), prog, len(rows), _lib.ptr(counts), None, 0))
     named = dict(zip(MPS_TRAJECTORY_COUNTS, (int(c) for c in counts)))
     if not return_schedule:
         return named
     sched = np.zeros(int(counts[6]), dtype=_lib.OP_DTYPE)
-    _lib.check(_lib.load().aqc_mps_traj_plan(int(n), prog, len(rows), _lib.ptr(counts), _lib.ptr(sched), len(sched)))
+    _lib.check(entry(int(n), prog, len(rows), _lib.ptr(counts), _lib.ptr(sched), len(sched)))
     return named, sched
 
 

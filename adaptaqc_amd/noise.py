@@ -1,7 +1,7 @@
 """Noise models for the shot backend: one-qubit Kraus channels attached to instruction names, and the
 flat program the device's trajectory samplers run (csrc/traj.hip, aqc_sv_traj_sample, on a statevector;
 csrc/mps_traj.hip, aqc_mps_traj_sample, on an MPS), and the POVM effects of a noisy Pauli-basis
-readout for noisy pair tomography (``readout_effects``, aqc_sv_traj_pair_tomo).
+readout for noisy pair tomography (``readout_effects``, aqc_sv_traj_pair_tomo / aqc_mps_traj_pair_tomo).
 
 Stands in for the parts of ``qiskit_aer.noise`` that the reference uses
 (``execute_kwargs={'noise_model': NoiseModel, 'shots': ...}``, approximate_compiler.py:93;
@@ -208,7 +208,7 @@ _SDG = np.diag([1.0 + 0j, -1j])
 
 def readout_effects(n, noise_model):
     """float64 [n, 3, 2, 4]: the POVM effects of a noisy Pauli-basis measurement of every qubit, as
-    aqc_sv_traj_pair_tomo takes them -- entry [q, b, o] holds (E00, E11, Re E01, Im E01) of the
+    aqc_sv_traj_pair_tomo and aqc_mps_traj_pair_tomo take them -- entry [q, b, o] holds (E00, E11, Re E01, Im E01) of the
     Hermitian 2x2 effect of qubit q, basis b (0 X, 1 Y, 2 Z), outcome o (0 the +1 eigenstate).
 
     The reference measures basis Y by appending ``sdg``, ``h``, ``measure`` (X: ``h``, ``measure``;

@@ -239,8 +239,42 @@ int aqc_mps_traj_sample(int n, int chi_cap, double threshold, int max_chi, const
    rows, Kraus rows, measurement rows, all rows. */
 #define AQC_OP_MEASURE1 2
 int aqc_mps_traj_plan(int n, const aqc_op_t* prog, int nprog, int* counts, aqc_op_t* sched, int sched_cap);
-/* Debugging: forces the batch size B of aqc_mps_traj_sample (1 .. 4096; 0 restores the default). */
+/* Debugging: forces the batch size B of aqc_mps_traj_sample and aqc_mps_traj_pair_tomo (1 .. 4096; 0
+   restores the default). */
 int aqc_mps_traj_set_batch(int batch);
+
+/* ---- noisy pair tomography above 24 qubits: aqc_sv_traj_pair_tomo on the MPS engine ---------------
+   The semantics of aqc_sv_traj_pair_tomo (pairs, effects, settings, draw rule, u layout, counts and
+   outcomes: see there) on the engine of aqc_mps_traj_sample.  ntraj = 9 nshots trajectories, each an
+   MPS |0...0> of capacity chi_cap with the truncation (threshold, max_chi); trajectory t = 9 i + s
+   serves setting s of EVERY pair.  A trajectory runs aqc_mps_traj_sample's schedule without the
+   measurement sweep: gate rows, Kraus rows at the tracked centre (same event numbering, choice rule
+   and folding K_k <- K_k P), then the flush of pending one-qubit gates and the sort.  For pair j, rho is
+   the 4x4 RDM of the trajectory's MPS (index 2 bit_hi + bit_lo) by the full contraction of
+   aqc_mps_pair_rdms_batch, which assumes no canonical form (a Kraus row breaks Vidal form);
+   p_o = max(0, Re Tr[(E[hi][b_hi][o_hi] (x) E[lo][b_lo][o_lo]) rho]), and one outcome by
+   aqc_multinomial_counts' rule with u = sample_uniform(seed, run, t, E + j), or u[t (E + npairs) + E + j]
+   when u is not NULL.  P is the sum of the four p_o, so a truncated trajectory (Tr rho < 1) needs no
+   renormalisation.
+   The trajectories run in batches of B handles and are read out R at a time: R = min(ntraj, 16, what
+   2 GiB hold of the RDM sweep's per-state workspace, at least 1), B = min(ntraj, 256, what 4 GiB less
+   that workspace hold of handles, at least 1); under a batch that aqc_mps_traj_set_batch forces, R is
+   what that batch leaves.  The count table accumulates on the device (integer atomics; no
+   floating-point atomics, every sum in a fixed order) and is copied back once.  An outcome depends on
+   (seed, run, t) only -- not on B, the readout sub-batch or nshots (fewer shots give a prefix): two
+   calls return the same bits.
+   AQC_ERR_ARG: as aqc_sv_traj_pair_tomo with n in 2 .. 4096, and chi_cap outside 1 .. 1024.
+   AQC_ERR_STATE ("capacity (chi_cap) exceeded") when a trajectory outgrows chi_cap: no output is valid
+   then. */
+int aqc_mps_traj_pair_tomo(int n, int chi_cap, double threshold, int max_chi, const aqc_op_t* prog, int nprog,
+                           const int* pairs, int npairs, const double* effects, int nshots, uint64_t seed, uint64_t run,
+                           const double* u, int64_t* counts, uint8_t* outcomes);
+/* aqc_mps_traj_plan for aqc_mps_traj_pair_tomo's schedule: no measurement rows (counts[5] = 0), the
+   last row belongs to the final sort or the flush. */
+int aqc_mps_traj_tomo_plan(int n, const aqc_op_t* prog, int nprog, int* counts, aqc_op_t* sched, int sched_cap);
+/* Debugging: forces the number of states per RDM sweep of aqc_mps_traj_pair_tomo's readout (1 .. 4096,
+   at most the batch; 0 restores the default). */
+int aqc_mps_traj_set_readout_batch(int batch);
 
 /* ---- Pauli-string expectation values: replaces circuit_operations_pauli_ops.py:60-100 -------------
    (expectation_value_of_pauli_operator, which runs one rotated circuit per term).
