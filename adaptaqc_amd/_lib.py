@@ -20,6 +20,7 @@ OP_DTYPE = np.dtype(
 assert OP_DTYPE.itemsize == 272
 OP_KRAUS1 = 1  # AQC_OP_KRAUS1: a Kraus row of aqc_sv_traj_sample / aqc_mps_traj_sample
 OP_MEASURE1 = 2  # AQC_OP_MEASURE1: a measurement row of aqc_mps_traj_plan's schedule
+OP_KRAUS2 = 3  # AQC_OP_KRAUS2: one operator of a correlated two-qubit Kraus group (flags | k << 8 | nk << 16)
 
 # every symbol declared in include/aqc_hip.h (the drop-in boundary) and include/aqc_hip_diag.h
 # (diagnostics and test hooks)

@@ -174,12 +174,21 @@ class SamplingSimulator:
                     "a noise model runs as statevector trajectories (method 'statevector', or 'automatic' up to "
                     f"{self.MAX_NOISY_QUBITS} qubits) unless the simulator is built with mps_trajectories=True, "
                     "which runs it as MPS trajectories")
+            self._refuse_correlated_on_mps(rows)
             return rows, n_events, "matrix_product_state"
         if n > self.MAX_NOISY_QUBITS:
             raise NotImplementedError(
                 f"statevector trajectories stop at {self.MAX_NOISY_QUBITS} qubits: use method 'automatic' or "
                 "'matrix_product_state' with mps_trajectories=True")
         return rows, n_events, "statevector"
+
+    @staticmethod
+    def _refuse_correlated_on_mps(rows):
+        """A program with a correlated two-qubit Kraus group cannot run on the MPS trajectory engine."""
+        from ..noise import _CORRELATED_ON_MPS, has_correlated_rows
+
+        if has_correlated_rows(rows):
+            raise NotImplementedError(f"noise_model: {_CORRELATED_ON_MPS}")
 
     def _at_learned_capacity(self, n, call):
         """``call(chi_cap=, threshold=, max_chi=)`` -- a batch of MPS trajectories of n qubits -- at the
@@ -380,6 +389,7 @@ class QiskitSamplingBackend(AQCBackend):
         sim = self.simulator
         method = sim.options.method
         if sim._trajectory_engine(n) == "matrix_product_state" and sim.mps_trajectories:
+            sim._refuse_correlated_on_mps(rows)
             return rows, n_events, readout_effects(n, noise_model), "matrix_product_state"
         if method == "matrix_product_state":
             raise NotImplementedError("trajectory_tomography runs statevector trajectories: a noise_model with "

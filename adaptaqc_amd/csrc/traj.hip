@@ -7,6 +7,9 @@
 // C_k and P = C_last, event e takes the smallest k with C_k > u_e P (where rounding leaves none, the
 // last k with p_k > 0) and psi <- K_k psi / sqrt(p_k).  The final draw is aqc_sv_sample's rule with
 // u_E.  u_e = sample_uniform(seed, run, shot, e): an outcome depends on (seed, run, shot) only.
+// A correlated two-qubit channel (AQC_OP_KRAUS2) is a group of nk <= 16 consecutive rows, one 4x4
+// operator each, on the qubits (q0, q1) of the gate it follows: one event with the same choice rule,
+// the chosen operator applied to both qubits.
 //
 // k_sv_traj: one workgroup carries one trajectory from |0...0> to its outcome and loops over the
 // shots wg, wg + grid, ...; no workgroup waits for another.  Up to 13 qubits the state lives in
@@ -18,6 +21,15 @@
 //               summed per thread in pair order, over the wave by a butterfly, over the waves in
 //               index order), p_k = Re Tr(K_k^dag K_k rho) with K_k^dag K_k multiplied on the host,
 //               then an apply pass with K_k / sqrt(p_k)
+//   Kraus group on its first row: where every K_k^dag K_k is a multiple of I (Pauli and other
+//               mixed-unitary channels) p_k is that multiple and no pass reads the state; else one
+//               reduction pass over the amplitude quadruples of (q0, q1) for the 4 real and 6
+//               complex entries of the 4x4 reduced density matrix (same order: thread, wave
+//               butterfly, waves in index order), p_k = max(0, Re Tr(K_k^dag K_k rho)).  The
+//               weights and the chosen operator are read from the global program (uniform
+//               addresses), never from the staged chunk, which a group may overrun; the chosen
+//               K_k / sqrt(p_k) replaces the first row's matrix in LDS and the gate row's quad
+//               pass applies it.  The group's other rows are skipped.
 //   final draw  thread t sums its contiguous amplitudes in order, a wave scan, the wave totals
 //               in order; the first thread whose inclusive sum exceeds u_E P walks its amplitudes
 // No atomics anywhere: two calls return the same bits.
@@ -56,15 +68,17 @@ constexpr int kMaxShots = 1 << 30;
 constexpr int kMaxGlobalWgs = 256;  // global-workspace path: at most 256 workgroups and 512 MB
 constexpr size_t kMaxGlobalBytes = (size_t)512 << 20;
 
-enum { kGate1 = 0, kGate2 = 1, kKraus = 2 };
+enum { kGate1 = 0, kGate2 = 1, kKraus = 2, kKraus2 = 3 };
 enum { kLds = 0, kGlobal = 1 };
 enum { kEndDraw = 0, kEndPairs = 1 };  // a trajectory's ending: the full-register draw, or the pair readout
 constexpr int kMaxPairs = 4096;
 
 // A program row as the kernel reads it.  Gate: m = the 2x2 / 4x4 matrix.  Kraus: m[8k ..] = K_k,
-// w[4k ..] = (M00, M11, Re M01, Im M01) of M = K_k^dag K_k, ev = the event index.
+// w[4k ..] = (M00, M11, Re M01, Im M01) of M = K_k^dag K_k, ev = the event index.  Kraus2 (one row per
+// operator of a group): m = the 4x4 K_k, w = M = K_k^dag K_k as M00 M11 M22 M33, then (Re, Im) of M01
+// M02 M03 M12 M13 M23; k = the row's place in its group; flat (first row): every M a multiple of I.
 struct TrajRow {
-  int32_t kind, q0, q1, nk, ev, pad[3];
+  int32_t kind, q0, q1, nk, ev, k, flat, pad;
   double m[32];
   double w[16];
 };
@@ -89,8 +103,15 @@ struct TrajJob {
 };
 
 // bytes of dynamic LDS beside the state
-constexpr size_t kSideBytes = kChunk * sizeof(TrajRow) + kChunk * sizeof(double) + kMaxWaves * 4 * sizeof(double) +
-                              kMaxWaves * sizeof(double) + kMaxWaves * sizeof(int);
+// The kernel is compiled twice (its K2 parameter): a program without a Kraus group runs the variant
+// without the group code, whose registers and side area are what the one-qubit rows need.
+constexpr int kRedWords = 16;  // doubles per wave in the reduction area with groups: their 4x4 RDM
+constexpr size_t side_bytes(bool k2) {
+  return kChunk * sizeof(TrajRow) + kChunk * sizeof(double) + kMaxWaves * (k2 ? kRedWords : 4) * sizeof(double) +
+         kMaxWaves * sizeof(double) + (k2 ? (16 + kRedWords) * sizeof(double) : 0) + kMaxWaves * sizeof(int);
+}
+static_assert(((size_t)1 << kLdsMaxQubits) * sizeof(cplx) + side_bytes(true) <= (size_t)160 * 1024,
+              "the largest LDS-resident state and the side area fit a CU's LDS");
 
 template <int MODE>
 struct Amps;
@@ -121,7 +142,7 @@ __device__ __forceinline__ double wave_scan(double v, int lane) {
   return v;
 }
 
-template <int MODE, int END>
+template <int MODE, int END, bool K2>
 __global__ __launch_bounds__(kMaxThreads) void k_sv_traj(const TrajJob j) {
   extern __shared__ double2 traj_lds[];
   const int tid = threadIdx.x, T = blockDim.x, lane = tid & 63, wave = tid >> 6, nwaves = T >> 6;
@@ -132,9 +153,11 @@ __global__ __launch_bounds__(kMaxThreads) void k_sv_traj(const TrajJob j) {
   else psi.a = j.ws + (size_t)blockIdx.x * dim;
   TrajRow* rows = (TrajRow*)(traj_lds + lds_amps);
   double* ul = (double*)(rows + kChunk);  // the chunk's uniforms
-  double* red = ul + kChunk;              // [wave][4]
-  double* wtot = red + kMaxWaves * 4;     // [wave]
-  int* wlast = (int*)(wtot + kMaxWaves);  // [wave]
+  double* red = ul + kChunk;              // [wave][4], with groups [wave][kRedWords]
+  double* wtot = red + kMaxWaves * (K2 ? kRedWords : 4);  // [wave]
+  double* pkl = wtot + kMaxWaves;         // K2 only, [16]: a Kraus group's weights p_k
+  double* rho = pkl + 16;                 // K2 only, [kRedWords]: a Kraus group's reduced density matrix
+  int* wlast = (int*)(K2 ? rho + kRedWords : pkl);  // [wave]
   const int nev = j.nev;
 
   for (int shot = blockIdx.x; shot < j.nshots; shot += gridDim.x) {
@@ -144,7 +167,8 @@ __global__ __launch_bounds__(kMaxThreads) void k_sv_traj(const TrajJob j) {
       __syncthreads();  // the previous chunk's last row has been applied
       for (int w = tid; w < nc * kRowWords; w += T)
         ((double2*)rows)[w] = reinterpret_cast<const double2*>(j.prog + c0)[w];
-      if (tid < nc && j.prog[c0 + tid].kind == kKraus) {
+      // an event's uniform sits at its (first) row's place in the chunk
+      if (tid < nc && (j.prog[c0 + tid].kind == kKraus || (K2 && j.prog[c0 + tid].kind == kKraus2 && j.prog[c0 + tid].k == 0))) {
         const int e = j.prog[c0 + tid].ev;
         ul[tid] = j.u ? j.u[(size_t)shot * j.ustride + e] : aqc::sample_uniform(j.seed, j.run, (uint64_t)shot, (uint32_t)e);
       }
@@ -152,7 +176,92 @@ __global__ __launch_bounds__(kMaxThreads) void k_sv_traj(const TrajJob j) {
         const TrajRow& r = rows[gi];
         __syncthreads();
         const int kind = r.kind;
-        if (kind == kGate2) {
+        if (K2 && kind == kKraus2) {
+          if (r.k != 0) continue;  // the group was served on its first row
+          const TrajRow* grp = j.prog + (c0 + gi);  // the group's rows in the global program
+          const int nk = r.nk, flat = r.flat;
+          if (!flat) {
+            const int t0 = r.q0, t1 = r.q1;
+            const int lo = t0 < t1 ? t0 : t1, hi = t0 < t1 ? t1 : t0;
+            double d[4] = {0.0, 0.0, 0.0, 0.0};  // rho_ss; rho_st = sum a_s conj(a_t), s < t
+            double ox[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, oy[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+            for (int p = tid; p < quarter; p += T) {
+              const int b = insert_zero(insert_zero(p, lo), hi);
+              cplx a[4];
+#pragma unroll
+              for (int s = 0; s < 4; ++s) a[s] = psi.ld(b | ((s & 1) << t0) | ((s >> 1) << t1));
+              int c = 0;
+#pragma unroll
+              for (int s = 0; s < 4; ++s) {
+                d[s] += aqc::cnorm2(a[s]);
+#pragma unroll
+                for (int t = s + 1; t < 4; ++t, ++c) {
+                  const cplx z = aqc::cmulc(a[s], a[t]);
+                  ox[c] += z.x;
+                  oy[c] += z.y;
+                }
+              }
+            }
+#pragma unroll
+            for (int s = 0; s < 4; ++s) d[s] = wave_sum(d[s]);
+#pragma unroll
+            for (int c = 0; c < 6; ++c) {
+              ox[c] = wave_sum(ox[c]);
+              oy[c] = wave_sum(oy[c]);
+            }
+            if (lane == 0) {
+              double* rw = red + kRedWords * wave;
+#pragma unroll
+              for (int s = 0; s < 4; ++s) rw[s] = d[s];
+#pragma unroll
+              for (int c = 0; c < 6; ++c) {
+                rw[4 + 2 * c] = ox[c];
+                rw[5 + 2 * c] = oy[c];
+              }
+            }
+            __syncthreads();
+            if (tid < kRedWords) {  // entry tid of rho: the waves' sums in index order
+              double x = 0.0;
+              for (int wv = 0; wv < nwaves; ++wv) x += red[kRedWords * wv + tid];
+              rho[tid] = x;
+            }
+            __syncthreads();
+          }
+          // thread q < nk: p_q = max(0, Re Tr(M_q rho)); a flat group's p_q is M_q[0][0] (rho has trace 1)
+          if (tid < nk) {
+            const double* w = grp[tid].w;
+            double p = w[0];
+            if (!flat) {
+              p = w[0] * rho[0] + w[1] * rho[1] + w[2] * rho[2] + w[3] * rho[3];
+              double o = 0.0;
+#pragma unroll
+              for (int e = 4; e < kRedWords; ++e) o += w[e] * rho[e];
+              p += 2.0 * o;
+            }
+            pkl[tid] = fmax(0.0, p);
+          }
+          __syncthreads();
+          // every thread takes the same weights in the same order, so all choose the same k
+          double P = 0.0;
+          for (int q = 0; q < nk; ++q) P += pkl[q];
+          const double target = ul[gi] * P;
+          int k = -1, lastnz = 0;
+          double c = 0.0;
+          for (int q = 0; q < nk; ++q) {
+            const double pq = pkl[q];
+            c += pq;
+            if (pq > 0.0) lastnz = q;
+            if (k < 0 && c > target) k = q;
+          }
+          if (k < 0) k = lastnz;
+          const double psel = pkl[k];
+          const double sc = psel > 0.0 ? 1.0 / sqrt(psel) : 0.0;
+          if (tid == 0 && j.choices) j.choices[(size_t)shot * nev + r.ev] = (uint8_t)k;
+          // the chosen operator, scaled, takes the place of K_0 in the staged row (restaged every shot)
+          if (tid < 16) ((cplx*)rows[gi].m)[tid] = aqc::cscale(((const cplx*)grp[k].m)[tid], sc);
+          __syncthreads();
+        }
+        if (kind == kGate2 || (K2 && kind == kKraus2)) {
           const int t0 = r.q0, t1 = r.q1;
           const int lo = t0 < t1 ? t0 : t1, hi = t0 < t1 ? t1 : t0;
           const cplx* m = (const cplx*)r.m;
@@ -354,7 +463,55 @@ int fail(const std::string& msg) {
   return AQC_ERR_ARG;
 }
 
-// validates the program and writes its device rows; *nev = the number of Kraus rows
+// the nk rows of a correlated group whose first row (k = 0, nk, qubits) has been checked: every row's
+// flags and qubits, finite entries, M_k = K_k^dag K_k into w, sum M_k = I within 1e-9
+int build_group(const aqc_op_t* ops, int nk, TrajRow* out, int ev) {
+  double sum[16] = {0.0};
+  bool flat = true;
+  for (int k = 0; k < nk; ++k) {
+    const aqc_op_t& op = ops[k];
+    if (op.flags != (AQC_OP_KRAUS2 | (k << 8) | (nk << 16)) || op.nq != 2 || op.q0 != ops[0].q0 || op.q1 != ops[0].q1)
+      return fail("malformed Kraus group: rows k = 0 .. nk-1 in order on the same qubits");
+    for (int e = 0; e < 32; ++e)
+      if (!std::isfinite(op.m[e])) return fail("malformed Kraus group: a matrix entry is not finite");
+    TrajRow& r = out[k];
+    r.kind = kKraus2;
+    r.q0 = op.q0;
+    r.q1 = op.q1;
+    r.nk = nk;
+    r.ev = ev;
+    r.k = k;
+    std::memcpy(r.m, op.m, 32 * sizeof(double));
+    // M_st = sum_r conj(K_rs) K_rt; K_rs = m[2 (4 r + s)] + i m[2 (4 r + s) + 1]
+    int c = 0;
+    for (int s = 0; s < 4; ++s)
+      for (int t = s; t < 4; ++t) {
+        double x = 0.0, y = 0.0;
+        for (int q = 0; q < 4; ++q) {
+          const double ar = op.m[2 * (4 * q + s)], ai = op.m[2 * (4 * q + s) + 1];
+          const double br = op.m[2 * (4 * q + t)], bi = op.m[2 * (4 * q + t) + 1];
+          x += ar * br + ai * bi;
+          y += ar * bi - ai * br;
+        }
+        if (t == s) {
+          r.w[s] = x;
+          sum[s] += x;
+          if (std::fabs(x - r.w[0]) > 1e-12) flat = false;
+        } else {
+          r.w[4 + 2 * c] = x, r.w[5 + 2 * c] = y;
+          sum[4 + 2 * c] += x, sum[5 + 2 * c] += y;
+          if (std::fabs(x) > 1e-12 || std::fabs(y) > 1e-12) flat = false;
+          ++c;
+        }
+      }
+  }
+  for (int e = 0; e < 16; ++e)
+    if (std::fabs(sum[e] - (e < 4 ? 1.0 : 0.0)) > 1e-9) return fail("Kraus group: sum K^dag K is not the identity");
+  out[0].flat = flat ? 1 : 0;
+  return AQC_OK;
+}
+
+// validates the program and writes its device rows; *nev = the number of events (Kraus rows and groups)
 int build_rows(int n, const aqc_op_t* prog, int nprog, std::vector<TrajRow>& rows, int* nev) {
   rows.assign((size_t)nprog, TrajRow());
   int ev = 0;
@@ -391,6 +548,13 @@ int build_rows(int n, const aqc_op_t* prog, int nprog, std::vector<TrajRow>& row
       }
       if (std::fabs(s00 - 1.0) > 1e-9 || std::fabs(s11 - 1.0) > 1e-9 || std::fabs(sx) > 1e-9 || std::fabs(sy) > 1e-9)
         return fail("Kraus row: sum K^dag K is not the identity");
+    } else if ((op.flags & 0xff) == AQC_OP_KRAUS2) {
+      const int nk = (op.flags >> 16) & 0xff;
+      if (op.flags != (AQC_OP_KRAUS2 | (nk << 16)) || nk < 1 || nk > 16 || nk > nprog - i)
+        return fail("malformed Kraus group: its first row needs k = 0 and 1 .. 16 operators within the program");
+      if (op.q0 < 0 || op.q0 >= n || op.q1 < 0 || op.q1 >= n || op.q0 == op.q1) return fail("Kraus group: bad qubits");
+      if (int rc = build_group(prog + i, nk, &rows[i], ev++)) return rc;
+      i += nk - 1;
     } else {
       return fail("unknown row flags");
     }
@@ -405,14 +569,14 @@ int threads_for(int n) {  // a quarter of the amplitudes, within 64 .. 512
 }
 
 // workgroups for ntraj trajectories of n qubits
-int grid_for(int n, int ntraj, int threads, int* grid) {
+int grid_for(int n, int ntraj, int threads, bool k2, int* grid) {
   const size_t dim = (size_t)1 << n;
   if (n <= kLdsMaxQubits) {
     int dev = 0, cus = 0;
     AQC_HIP_CHECK(hipGetDevice(&dev));
     AQC_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     // workgroups that fit a CU together: LDS (160 KB), 32 waves, and at most 8
-    const size_t lds = dim * sizeof(cplx) + kSideBytes;
+    const size_t lds = dim * sizeof(cplx) + side_bytes(k2);
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>({(size_t)160 * 1024 / lds, (size_t)(2048 / threads), 8}));
     *grid = (int)std::min<size_t>((size_t)ntraj, (size_t)std::max(cus, 1) * per_cu);
   } else {
@@ -422,11 +586,19 @@ int grid_for(int n, int ntraj, int threads, int* grid) {
   return AQC_OK;
 }
 
-template <int MODE, int END>
-int launch(const TrajJob& j, int grid, int threads, size_t dyn) {
-  if (int e = aqc::allow_dynamic_lds((const void*)k_sv_traj<MODE, END>, (int)dyn)) return e;
-  hipLaunchKernelGGL((k_sv_traj<MODE, END>), dim3(grid), dim3(threads), dyn, 0, j);
+template <int MODE, int END, bool K2>
+int launch_as(const TrajJob& j, int grid, int threads) {
+  const size_t dyn = (MODE == kLds ? ((size_t)1 << j.n) * sizeof(cplx) : 0) + side_bytes(K2);
+  if (int e = aqc::allow_dynamic_lds((const void*)k_sv_traj<MODE, END, K2>, (int)dyn)) return e;
+  hipLaunchKernelGGL((k_sv_traj<MODE, END, K2>), dim3(grid), dim3(threads), dyn, 0, j);
   return AQC_OK;
+}
+
+// k2: the program holds a Kraus group
+template <int END>
+int launch(const TrajJob& j, int grid, int threads, bool in_lds, bool k2) {
+  if (in_lds) return k2 ? launch_as<kLds, END, true>(j, grid, threads) : launch_as<kLds, END, false>(j, grid, threads);
+  return k2 ? launch_as<kGlobal, END, true>(j, grid, threads) : launch_as<kGlobal, END, false>(j, grid, threads);
 }
 
 }  // namespace
@@ -440,6 +612,7 @@ extern "C" int aqc_sv_traj_sample(int n, const aqc_op_t* prog, int nprog, int ns
   std::vector<TrajRow> rows;
   int nev = 0;
   if (int rc = build_rows(n, prog, nprog, rows, &nev)) return rc;
+  const bool k2 = std::any_of(rows.begin(), rows.end(), [](const TrajRow& r) { return r.kind == kKraus2; });
   const size_t nu = (size_t)nshots * (nev + 1);
   if (u)
     for (size_t e = 0; e < nu; ++e)
@@ -449,7 +622,7 @@ extern "C" int aqc_sv_traj_sample(int n, const aqc_op_t* prog, int nprog, int ns
   const bool in_lds = n <= kLdsMaxQubits;
   const int threads = threads_for(n);
   int grid = 0;
-  if (int rc = grid_for(n, nshots, threads, &grid)) return rc;
+  if (int rc = grid_for(n, nshots, threads, k2, &grid)) return rc;
   const size_t pb = up256(std::max<size_t>(1, rows.size()) * sizeof(TrajRow));
   const size_t ub = u ? up256(nu * sizeof(double)) : 0;
   const size_t ob = up256((size_t)nshots * sizeof(uint64_t));
@@ -478,8 +651,7 @@ extern "C" int aqc_sv_traj_sample(int n, const aqc_op_t* prog, int nprog, int ns
     AQC_HIP_CHECK(hipMemcpyAsync(buf, rows.data(), rows.size() * sizeof(TrajRow), hipMemcpyHostToDevice, st));
   if (u) AQC_HIP_CHECK(hipMemcpyAsync(buf + pb, u, nu * sizeof(double), hipMemcpyHostToDevice, st));
   aqc::KernelTimer::begin(st, "sv_traj", 0.0, (double)nshots * (double)nprog * (double)dim * 14.0);
-  const int rc = in_lds ? launch<kLds, kEndDraw>(j, grid, threads, dim * sizeof(cplx) + kSideBytes)
-                        : launch<kGlobal, kEndDraw>(j, grid, threads, kSideBytes);
+  const int rc = launch<kEndDraw>(j, grid, threads, in_lds, k2);
   aqc::KernelTimer::end(st);
   if (rc != AQC_OK) return rc;
   AQC_CHECK_LAUNCH();
@@ -506,6 +678,7 @@ extern "C" int aqc_sv_traj_pair_tomo(int n, const aqc_op_t* prog, int nprog, con
   std::vector<TrajRow> rows;
   int nev = 0;
   if (int rc = build_rows(n, prog, nprog, rows, &nev)) return rc;
+  const bool k2 = std::any_of(rows.begin(), rows.end(), [](const TrajRow& r) { return r.kind == kKraus2; });
   const int ntraj = 9 * nshots;
   const int ustride = nev + npairs;
   const size_t nu = (size_t)ntraj * ustride;
@@ -516,7 +689,7 @@ extern "C" int aqc_sv_traj_pair_tomo(int n, const aqc_op_t* prog, int nprog, con
   const bool in_lds = n <= kLdsMaxQubits;
   const int threads = threads_for(n);
   int grid = 0;
-  if (int rc = grid_for(n, ntraj, threads, &grid)) return rc;
+  if (int rc = grid_for(n, ntraj, threads, k2, &grid)) return rc;
   const size_t pb = up256(std::max<size_t>(1, rows.size()) * sizeof(TrajRow));
   const size_t ub = u ? up256(nu * sizeof(double)) : 0;
   const size_t qb = up256((size_t)npairs * 2 * sizeof(int));
@@ -554,8 +727,7 @@ extern "C" int aqc_sv_traj_pair_tomo(int n, const aqc_op_t* prog, int nprog, con
   AQC_HIP_CHECK(hipMemsetAsync(j.counts, 0, (size_t)npairs * 36 * sizeof(int64_t), st));
   aqc::KernelTimer::begin(st, "sv_traj_pair_tomo", 0.0,
                           (double)ntraj * ((double)nprog * 14.0 + (double)npairs * 10.0) * (double)dim);
-  const int rc = in_lds ? launch<kLds, kEndPairs>(j, grid, threads, dim * sizeof(cplx) + kSideBytes)
-                        : launch<kGlobal, kEndPairs>(j, grid, threads, kSideBytes);
+  const int rc = launch<kEndPairs>(j, grid, threads, in_lds, k2);
   aqc::KernelTimer::end(st);
   if (rc != AQC_OK) return rc;
   AQC_CHECK_LAUNCH();

@@ -275,15 +275,30 @@ def sample_uniforms(seed, run, shots, nper):
     return out
 
 
+def _count_events(rows):
+    """The events of a trajectory program: its one-qubit Kraus rows plus its correlated groups."""
+    from .noise import count_events
+
+    return count_events(rows)
+
+
+def _refuse_correlated_rows(rows, what):
+    from .noise import _CORRELATED_ON_MPS, has_correlated_rows
+
+    if has_correlated_rows(rows):
+        raise NotImplementedError(f"{what}: {_CORRELATED_ON_MPS}")
+
+
 def trajectory_sample(n, rows, n_events, shots, seed, run=0, u=None, return_choices=False):
     """``shots`` noisy shots as quantum trajectories (aqc_sv_traj_sample): uint64[shots] basis indices
-    (bit q = qubit q) of the program ``rows`` (noise.trajectory_program) on n qubits, whose Kraus rows
-    number ``n_events``.  ``u``: [shots, n_events + 1] uniforms in [0, 1) used instead of the
-    generator's (event e in column e, the final draw last).  With ``return_choices`` also the
-    uint8[shots, n_events] Kraus operator chosen at every event."""
+    (bit q = qubit q) of the program ``rows`` (noise.trajectory_program) on n qubits, whose events
+    (one-qubit Kraus rows and correlated two-qubit groups) number ``n_events``.  ``u``: [shots,
+    n_events + 1] uniforms in [0, 1) used instead of the generator's (event e in column e, the final
+    draw last).  With ``return_choices`` also the uint8[shots, n_events] Kraus operator (0 .. 15 for a
+    correlated group) chosen at every event."""
     shots, n_events = int(shots), int(n_events)
     rows = np.ascontiguousarray(rows, dtype=_lib.OP_DTYPE)
-    if int(np.count_nonzero(rows["flags"] == _lib.OP_KRAUS1)) != n_events:
+    if _count_events(rows) != n_events:
         raise ValueError("trajectory_sample: n_events does not match the program's Kraus rows")
     out = np.zeros(max(shots, 0), dtype=np.uint64)
     up = _uniforms_arg(u, (shots, n_events + 1))
@@ -304,7 +319,7 @@ def trajectory_pair_tomography(n, rows, n_events, pairs, effects, shots, seed, r
     [9 shots, npairs] outcome o = 2 o_hi + o_lo every trajectory drew for every pair."""
     n, shots, n_events = int(n), int(shots), int(n_events)
     rows = np.ascontiguousarray(rows, dtype=_lib.OP_DTYPE)
-    if int(np.count_nonzero(rows["flags"] == _lib.OP_KRAUS1)) != n_events:
+    if _count_events(rows) != n_events:
         raise ValueError("trajectory_pair_tomography: n_events does not match the program's Kraus rows")
     pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
     npairs = len(pr)
@@ -334,6 +349,7 @@ def mps_trajectory_sample(n, rows, n_events, shots, seed, run=0, u=None, return_
     operator chosen at every event."""
     shots, n_events, n = int(shots), int(n_events), int(n)
     rows = np.ascontiguousarray(rows, dtype=_lib.OP_DTYPE)
+    _refuse_correlated_rows(rows, "mps_trajectory_sample")
     if int(np.count_nonzero(rows["flags"] == _lib.OP_KRAUS1)) != n_events:
         raise ValueError("mps_trajectory_sample: n_events does not match the program's Kraus rows")
     out = np.zeros((max(shots, 0), (max(n, 1) + 63) // 64), dtype=np.uint64)
@@ -356,6 +372,7 @@ def mps_trajectory_pair_tomography(n, rows, n_events, pairs, effects, shots, see
     the capacity AqcError."""
     n, shots, n_events = int(n), int(shots), int(n_events)
     rows = np.ascontiguousarray(rows, dtype=_lib.OP_DTYPE)
+    _refuse_correlated_rows(rows, "mps_trajectory_pair_tomography")
     if int(np.count_nonzero(rows["flags"] == _lib.OP_KRAUS1)) != n_events:
         raise ValueError("mps_trajectory_pair_tomography: n_events does not match the program's Kraus rows")
     pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
@@ -388,6 +405,7 @@ def mps_trajectory_plan(n, rows, return_schedule=False, measure=True):
     ``measure=False``: the schedule of ``mps_trajectory_pair_tomography`` (aqc_mps_traj_tomo_plan), which
     ends with the sort, before the measurement sweep."""
     rows = np.ascontiguousarray(rows, dtype=_lib.OP_DTYPE)
+    _refuse_correlated_rows(rows, "mps_trajectory_plan")
     counts = np.zeros(7, dtype=np.int32)
     prog = _lib.ptr(rows) if len(rows) else None
     entry = _lib.load().aqc_mps_traj_plan if measure else _lib.load().aqc_mps_traj_tomo_plan

@@ -1,5 +1,6 @@
-"""Noise models for the shot backend: one-qubit Kraus channels attached to instruction names, and the
-flat program the device's trajectory samplers run (csrc/traj.hip, aqc_sv_traj_sample, on a statevector;
+"""Noise models for the shot backend: one-qubit Kraus channels, products of two of them, and correlated
+two-qubit Kraus sets (``QuantumError.two_qubit``, ``depolarizing_error(p, 2)``, two-letter
+``pauli_error`` labels) attached to instruction names, and the flat program the device's trajectory samplers run (csrc/traj.hip, aqc_sv_traj_sample, on a statevector;
 csrc/mps_traj.hip, aqc_mps_traj_sample, on an MPS), and the POVM effects of a noisy Pauli-basis
 readout for noisy pair tomography (``readout_effects``, aqc_sv_traj_pair_tomo / aqc_mps_traj_pair_tomo).
 
@@ -10,11 +11,19 @@ shot is one quantum trajectory: after every gate that carries an error, one Krau
 affected qubit's channel is drawn with probability |K_k psi|^2 and applied.  The law of the counts is
 that of the channel; the individual trajectories depend on the Kraus decomposition chosen here.
 
-Out of scope: correlated two-qubit Kraus sets, readout-error matrices, reset.
+A correlated error follows a two-qubit gate as one event: one of its 1-16 4x4 operators is drawn with
+probability |K_k psi|^2 and applied to both qubits (matrix index 2 b(second listed qubit) + b(first
+listed qubit), a two-qubit gate row's and Aer's convention).  It runs on the statevector trajectory
+engine (up to 24 qubits); the MPS trajectory engine refuses it by name.
+
+Out of scope: correlated errors on the MPS engine, two errors on one instruction, readout-error
+matrices, reset, errors on gates of three or more qubits.
 """
 import numpy as np
 
 _TOL = 1e-9
+_CORRELATED_ON_MPS = ("correlated two-qubit errors run on the statevector trajectory engine only (at most 24 "
+                      "qubits): the MPS trajectory engine does not support them yet")
 _PAULIS = {
     "I": np.eye(2, dtype=complex),
     "X": np.array([[0, 1], [1, 0]], dtype=complex),
@@ -24,15 +33,16 @@ _PAULIS = {
 
 
 class QuantumError:
-    """A one-qubit channel held as 1-4 Kraus matrices, or a two-qubit product of two such channels
-    (``expand`` / ``tensor``).  ``kraus``: a list of 2x2 complex matrices with sum K^dag K = I
-    within 1e-9."""
+    """A one-qubit channel held as 1-4 Kraus matrices, a two-qubit product of two such channels
+    (``expand`` / ``tensor``), or a correlated two-qubit channel of 1-16 4x4 Kraus matrices
+    (``two_qubit``).  ``kraus``: a list of 2x2 complex matrices with sum K^dag K = I within 1e-9."""
 
     def __init__(self, kraus):
         mats = [np.array(k, dtype=complex) for k in kraus]
         if mats and all(m.shape == (4, 4) for m in mats):
-            raise NotImplementedError("correlated two-qubit Kraus errors are not supported: build a product error "
-                                      "with expand() / tensor()")
+            raise NotImplementedError("QuantumError(kraus) takes one-qubit matrices: build a correlated two-qubit "
+                                      "error with QuantumError.two_qubit(kraus), a product error with expand() / "
+                                      "tensor()")
         if not 1 <= len(mats) <= 4 or any(m.shape != (2, 2) for m in mats):
             raise ValueError("QuantumError: 1 to 4 Kraus matrices of shape 2x2")
         total = sum(m.conj().T @ m for m in mats)
@@ -41,6 +51,23 @@ class QuantumError:
         self.kraus = mats
         self.pair = None  # (channel of the gate's first listed qubit, of its second)
         self._identity = all(np.max(np.abs(k - np.trace(k) / 2 * np.eye(2))) <= 1e-12 for k in mats)
+
+    @classmethod
+    def two_qubit(cls, kraus):
+        """A correlated two-qubit channel: 1 to 16 complex 4x4 matrices with sum K^dag K = I within 1e-9,
+        matrix index 2 b(second listed qubit) + b(first listed qubit) of the gate it follows."""
+        mats = [np.array(k, dtype=complex) for k in kraus]
+        if not 1 <= len(mats) <= 16 or any(m.shape != (4, 4) for m in mats):
+            raise ValueError("QuantumError.two_qubit: 1 to 16 Kraus matrices of shape 4x4")
+        if not all(np.all(np.isfinite(m)) for m in mats):
+            raise ValueError("QuantumError.two_qubit: a matrix entry is not finite")
+        if np.max(np.abs(sum(m.conj().T @ m for m in mats) - np.eye(4))) > _TOL:
+            raise ValueError("QuantumError.two_qubit: sum K^dag K is not the identity")
+        e = cls.__new__(cls)
+        e.kraus = mats
+        e.pair = None
+        e._identity = all(np.max(np.abs(k - np.trace(k) / 4 * np.eye(4))) <= 1e-12 for k in mats)
+        return e
 
     @classmethod
     def _product(cls, first, second):
@@ -53,8 +80,13 @@ class QuantumError:
         return e
 
     @property
+    def correlated(self):
+        """True for a two-qubit channel held as 4x4 Kraus matrices (``two_qubit``)."""
+        return self.pair is None and self.kraus[0].shape == (4, 4)
+
+    @property
     def num_qubits(self):
-        return 1 if self.pair is None else 2
+        return 2 if self.pair is not None or self.correlated else 1
 
     def expand(self, other):
         """The two-qubit product error with ``self`` on the gate's first listed qubit."""
@@ -69,14 +101,17 @@ class QuantumError:
         return self._identity
 
     def no_jump_weight(self):
-        """Tr(K_0^dag K_0) / 2 (the product over both qubits for a product error)."""
+        """Tr(K_0^dag K_0) / 2 (the product over both qubits for a product error; Tr(K_0^dag K_0) / 4
+        for a correlated one)."""
         if self.pair is not None:
             return self.pair[0].no_jump_weight() * self.pair[1].no_jump_weight()
-        return float(np.trace(self.kraus[0].conj().T @ self.kraus[0]).real / 2)
+        return float(np.trace(self.kraus[0].conj().T @ self.kraus[0]).real / len(self.kraus[0]))
 
     def __repr__(self):
         if self.pair is not None:
             return f"QuantumError(product of {self.pair[0]!r} and {self.pair[1]!r})"
+        if self.correlated:
+            return f"QuantumError({len(self.kraus)} Kraus, 2 qubits, correlated)"
         return f"QuantumError({len(self.kraus)} Kraus, 1 qubit)"
 
 
@@ -114,7 +149,15 @@ def phase_damping_error(lam):
 
 
 def pauli_error(terms):
-    """[(label, probability), ...] over the one-qubit labels I, X, Y, Z; the probabilities sum to 1."""
+    """[(label, probability), ...] over the one-qubit labels I, X, Y, Z, or over two-letter labels
+    (all of length 2: a correlated two-qubit error, the rightmost letter on the gate's first listed
+    qubit); the probabilities sum to 1."""
+    terms = list(terms)
+    width = {len(label) if isinstance(label, str) else 0 for label, _ in terms}
+    if width == {2}:
+        return _pauli_error2(terms)
+    if len(width) > 1 and width <= {1, 2}:
+        raise ValueError("pauli_error: labels of one length, 1 or 2")
     probs = {}
     for label, p in terms:
         if label not in _PAULIS:
@@ -127,9 +170,33 @@ def pauli_error(terms):
     return QuantumError([np.sqrt(p) * _PAULIS[label] for label, p in probs.items()])
 
 
-def depolarizing_error(p):
-    """rho -> (1 - p) rho + p I / 2 on one qubit (0 <= p <= 4/3), as Aer parametrises it."""
+def _pauli_error2(terms):
+    probs = {}
+    for label, p in terms:
+        if label[0] not in _PAULIS or label[1] not in _PAULIS:
+            raise ValueError("pauli_error: two-qubit labels of the letters I, X, Y, Z")
+        if not p >= 0:
+            raise ValueError("pauli_error: probabilities must not be negative")
+        probs[label] = probs.get(label, 0.0) + float(p)
+    if abs(sum(probs.values()) - 1) > _TOL:
+        raise ValueError("pauli_error: probabilities must sum to 1")
+    # the left letter is the second listed qubit, the high bit of the matrix index
+    return QuantumError.two_qubit([np.sqrt(p) * np.kron(_PAULIS[label[0]], _PAULIS[label[1]])
+                                   for label, p in probs.items()])
+
+
+def depolarizing_error(p, num_qubits=1):
+    """rho -> (1 - p) rho + p I / 2 on one qubit (0 <= p <= 4/3), as Aer parametrises it.  With
+    ``num_qubits=2`` the correlated rho -> (1 - p) rho + p I / 4 on two qubits (0 <= p <= 16/15): the
+    sixteen two-qubit Paulis, II first with weight 1 - 15 p / 16, p / 16 each for the others."""
     p = float(p)
+    if num_qubits == 2:
+        if not 0 <= p <= 16 / 15:
+            raise ValueError("depolarizing_error: p must lie in [0, 16/15] on two qubits")
+        rest = [a + b for a in "IXYZ" for b in "IXYZ"][1:]
+        return pauli_error([("II", max(0.0, 1 - 15 * p / 16))] + [(label, p / 16) for label in rest])
+    if num_qubits != 1:
+        raise ValueError("depolarizing_error: num_qubits must be 1 or 2")
     if not 0 <= p <= 4 / 3:
         raise ValueError("depolarizing_error: p must lie in [0, 4/3]")
     return pauli_error([("I", 1 - 3 * p / 4), ("X", p / 4), ("Y", p / 4), ("Z", p / 4)])
@@ -171,8 +238,10 @@ class NoiseModel:
         return dict(self._all)
 
     def channels(self, name, qubits):
-        """The one-qubit channels that follow instruction ``name`` on ``qubits``, as [(qubit, error)] in
-        the gate's qubit order (identity channels left out); [] for a noiseless instruction."""
+        """The channels that follow instruction ``name`` on ``qubits``: one-qubit channels as
+        [(qubit, error)] in the gate's qubit order, a correlated error on a two-qubit instruction as the
+        single entry [((qa, qb), error)] with the qubits in the gate's listed order (identity channels
+        left out); [] for a noiseless instruction."""
         qubits = tuple(int(q) for q in qubits)
         error = self._local.get((name, qubits), self._all.get(name))
         if error is None:
@@ -181,6 +250,8 @@ class NoiseModel:
             raise NotImplementedError(f"an error on the {len(qubits)}-qubit gate {name!r} is not supported")
         if error.num_qubits == 1:
             per_qubit = [error] * len(qubits)
+        elif len(qubits) == 2 and error.correlated:
+            return [] if error.is_identity() else [(qubits, error)]
         elif len(qubits) == 2:
             per_qubit = list(error.pair)
         else:
@@ -200,6 +271,34 @@ def kraus_row(error, qubit):
     row["nq"], row["q0"], row["q1"], row["flags"] = 1, int(qubit), len(error.kraus), _lib.OP_KRAUS1
     row["m"][0, : 8 * len(error.kraus)] = np.stack(error.kraus).reshape(-1).view(np.float64)
     return row
+
+
+def kraus2_rows(error, qubits):
+    """The group of aqc_op_t rows of a correlated error (flags AQC_OP_KRAUS2 | k << 8 | nk << 16): row k
+    holds the 4x4 operator K_k in m, q0 and q1 the gate's qubits in listed order."""
+    from . import _lib
+
+    nk = len(error.kraus)
+    rows = np.zeros(nk, dtype=_lib.OP_DTYPE)
+    rows["nq"], rows["q0"], rows["q1"] = 2, int(qubits[0]), int(qubits[1])
+    rows["flags"] = _lib.OP_KRAUS2 | (np.arange(nk) << 8) | (nk << 16)
+    rows["m"] = np.stack(error.kraus).reshape(nk, 16).view(np.float64)
+    return rows
+
+
+def has_correlated_rows(rows):
+    """True when the program holds a correlated two-qubit Kraus group (AQC_OP_KRAUS2 rows)."""
+    from . import _lib
+
+    return bool(np.any((np.asarray(rows["flags"]) & 0xFF) == _lib.OP_KRAUS2))
+
+
+def count_events(rows):
+    """The events of a program: its one-qubit Kraus rows plus its correlated groups (their first rows)."""
+    from . import _lib
+
+    flags = np.asarray(rows["flags"])
+    return int(np.count_nonzero(flags == _lib.OP_KRAUS1) + np.count_nonzero((flags & 0xFFFF) == _lib.OP_KRAUS2))
 
 
 _H = np.array([[1, 1], [1, -1]], dtype=complex) / np.sqrt(2)
@@ -243,9 +342,10 @@ def readout_effects(n, noise_model):
 def trajectory_program(circuit, noise_model):
     """(rows, n_events, measured): the flat program of aqc_sv_traj_sample for ``circuit`` under
     ``noise_model``.  Each gate of ``device_ops(circuit)`` is a gate row; after a gate that carries an
-    error one Kraus row follows per affected qubit, in the gate's qubit order; an error attached to
-    "measure" gives one Kraus row per measure instruction, in circuit order, after all gates.
-    Identity channels emit no row.  Event e numbers the Kraus rows in program order.  ``measured``:
+    error one Kraus row follows per affected qubit, in the gate's qubit order, or, for a correlated
+    error, one group of nk consecutive rows (``kraus2_rows``); an error attached to "measure" gives one
+    Kraus row per measure instruction, in circuit order, after all gates.  Identity channels emit no
+    row.  Event e numbers the one-qubit Kraus rows and the groups in program order.  ``measured``:
     {qubit: clbit}, or None for a circuit without measures (which must be terminal)."""
     from . import _lib
     from .backends.qiskit_sampling_backend import terminal_measurements
@@ -270,13 +370,25 @@ def trajectory_program(circuit, noise_model):
         slots += [(e, q) for q, e in channels]
     slots += tail
     is_kraus = np.fromiter((isinstance(s[0], QuantumError) for s in slots), dtype=bool, count=len(slots))
-    rows = np.zeros(len(slots), dtype=_lib.OP_DTYPE)
+    # a correlated channel takes one row per operator: first[i] = the first row of slot i
+    width = np.fromiter((len(s[0].kraus) if k and s[0].correlated else 1 for s, k in zip(slots, is_kraus)),
+                        dtype=np.int64, count=len(slots))
+    first = np.cumsum(width) - width
+    rows = np.zeros(int(width.sum()), dtype=_lib.OP_DTYPE)
     if len(slots) and not is_kraus.all():
-        rows[~is_kraus] = _lib.ops_array([s for s, k in zip(slots, is_kraus) if not k])
+        rows[first[~is_kraus]] = _lib.ops_array([s for s, k in zip(slots, is_kraus) if not k])
     by_error = {}
     for i in np.flatnonzero(is_kraus):
         by_error.setdefault(id(slots[i][0]), []).append(i)
-    for positions in by_error.values():
-        rows[positions] = kraus_row(slots[positions[0]][0], 0)[0]
-    rows["q0"][is_kraus] = [s[1] for s, k in zip(slots, is_kraus) if k]
+    for slot_ids in by_error.values():
+        error = slots[slot_ids[0]][0]
+        if error.correlated:
+            group = kraus2_rows(error, (0, 1))
+            for i in slot_ids:
+                rows[first[i]: first[i] + len(group)] = group
+                rows["q0"][first[i]: first[i] + len(group)] = slots[i][1][0]
+                rows["q1"][first[i]: first[i] + len(group)] = slots[i][1][1]
+        else:
+            rows[first[slot_ids]] = kraus_row(error, 0)[0]
+            rows["q0"][first[slot_ids]] = [slots[i][1] for i in slot_ids]
     return rows, int(is_kraus.sum()), measured

@@ -38,7 +38,7 @@ typedef struct aqc_op {
   int32_t nq;
   int32_t q0;
   int32_t q1;
-  int32_t flags; /* 0: a gate; AQC_OP_KRAUS1: a Kraus row of aqc_sv_traj_sample / aqc_mps_traj_sample only */
+  int32_t flags; /* 0: a gate; AQC_OP_KRAUS1 / AQC_OP_KRAUS2: a Kraus row of the trajectory samplers only */
   double m[32];
 } aqc_op_t;
 
@@ -171,8 +171,21 @@ int aqc_mps_sample(aqc_mps_t h, int nshots, uint64_t seed, uint64_t run, const d
    One workgroup carries a trajectory from start to outcome: up to 13 qubits with the state in LDS,
    from 14 to 24 on a slice of a global workspace (at most 256 workgroups and 512 MB: slow, but correct).
    AQC_ERR_ARG: n outside 1 .. 24, nshots outside 1 .. 2^30, a u outside [0, 1), a malformed row, or
-   a Kraus row whose sum K^dag K differs from the identity by more than 1e-9. */
+   a Kraus row whose sum K^dag K differs from the identity by more than 1e-9.
+   (flags & 0xff) == AQC_OP_KRAUS2: one operator of a correlated two-qubit channel on (q0, q1), the
+   qubits of the gate it follows in listed order (nq = 2).  A channel of nk operators (1 .. 16) is a
+   group of nk consecutive rows, row k with flags = AQC_OP_KRAUS2 | k << 8 | nk << 16 and m[0..31] =
+   the 4x4 matrix K_k, index 2 b(q1) + b(q0) as a two-qubit gate row's.  A group is ONE event: E counts
+   the one-qubit Kraus rows plus the groups in program order, the choice rule is the same over the
+   group's operators (p_k = |K_k psi|^2 = Re Tr(K_k^dag K_k rho) with rho the 4x4 reduced density
+   matrix of (q0, q1); where every K_k^dag K_k is a multiple of I within 1e-12, as for Pauli channels,
+   p_k is that multiple), and choices holds k = 0 .. 15.  aqc_sv_traj_sample and
+   aqc_sv_traj_pair_tomo take such rows; the MPS entry points answer AQC_ERR_ARG for them.
+   AQC_ERR_ARG, before any device call, also for a malformed group: k not running 0 .. nk-1 over
+   consecutive rows, nk outside 1 .. 16, differing qubits inside a group, q0 = q1 or a qubit out of
+   range, an entry that is not finite, sum K^dag K off the identity by more than 1e-9. */
 #define AQC_OP_KRAUS1 1
+#define AQC_OP_KRAUS2 3 /* (2 is AQC_OP_MEASURE1) */
 int aqc_sv_traj_sample(int n, const aqc_op_t* prog, int nprog, int nshots, uint64_t seed, uint64_t run,
                        const double* u, uint64_t* out, uint8_t* choices);
 
