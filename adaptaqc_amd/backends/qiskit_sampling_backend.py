@@ -241,6 +241,66 @@ class SamplingSimulator:
             counts = {k.rjust(width, "0"): v for k, v in counts.items()}
         return SamplingJob(SamplingResult(counts))
 
+    def _noisy_pauli_program(self, circuit, noise_model):
+        """(rows, n_events, effects) of the noisy Pauli readout on the statevector trajectory engine, or
+        None when ``noise_model`` has no effective error on the circuit or on the readout (one
+        simulation and binomial draws then)."""
+        from ..noise import readout_effects, trajectory_program
+
+        if noise_model is None:
+            return None
+        n = circuit.num_qubits
+        rows, n_events, _ = trajectory_program(without_classical_operations(circuit), noise_model)
+        readout = any(noise_model.channels(name, (q,)) for name in ("sdg", "h", "measure") for q in range(n))
+        if n_events == 0 and not readout:
+            return None
+        if self._trajectory_engine(n) == "matrix_product_state":
+            raise NotImplementedError("the Pauli readout of MPS trajectories is not built: pauli_terms='device' "
+                                      "under a noise model runs statevector trajectories (method 'statevector', or "
+                                      f"'automatic' up to {self.MAX_NOISY_QUBITS} qubits)")
+        if n > self.MAX_NOISY_QUBITS:
+            raise NotImplementedError(f"statevector trajectories stop at {self.MAX_NOISY_QUBITS} qubits, and the "
+                                      "Pauli readout of MPS trajectories is not built")
+        return rows, n_events, readout_effects(n, noise_model)
+
+    def pauli_counts(self, circuit, labels, shots=1024, seed_simulator=None, noise_model=None):
+        """int64 [len(labels)]: for every Pauli label (qiskit order, none all-identity) the number of +1
+        parities among ``shots`` shots of the reference's rotated and measured copy of ``circuit`` --
+        without building the copies.  The estimate of <P> is (2 plus - shots) / shots.
+
+        Under a ``noise_model`` with an effective error, ``shots`` trajectories of the circuit (without
+        its classical operations) run once and every one draws a +-1 outcome per term
+        (aqc_sv_traj_pauli_counts), the errors on the appended ``sdg`` / ``h`` / ``measure`` folded into
+        POVM effects (noise.readout_effects): each term's count has the law of its own noisy circuit;
+        different terms share trajectories and are correlated.  Statevector trajectories only.
+        Otherwise the circuit is simulated once (the cached state of ``run``), every term is taken by
+        ``pauli_expect`` and its count is one binomial draw on the device (aqc_multinomial_counts).
+        Seed and run counter as ``run``: one call advances the counter once."""
+        from ..device import multinomial_counts, trajectory_pauli_counts
+        from ..paulis import terms_to_codes
+
+        n = circuit.num_qubits
+        shots = int(shots)
+        codes = terms_to_codes(list(labels), n)
+        if len(codes) == 0:
+            return np.zeros(0, dtype=np.int64)
+        if not codes.any(axis=1).all():
+            raise ValueError("pauli_counts: an all-identity label has the value 1 and is not measured")
+        noisy = self._noisy_pauli_program(circuit, noise_model)
+        dev = self._state(circuit) if noisy is None else None
+        if seed_simulator is not None:
+            seed, run = int(seed_simulator), 0
+        else:
+            seed, run = self.seed, self.runs
+            self.runs += 1
+        if noisy is not None:
+            rows, n_events, effects = noisy
+            return trajectory_pauli_counts(n, rows, n_events, codes, effects, shots, seed, run)
+        ev = dev.pauli_expect(np.concatenate([codes, np.zeros((1, n), dtype=np.uint8)]))
+        v, w = ev[:-1], ev[-1]  # w = <psi|psi>: below 1 for a truncated MPS
+        probs = np.stack([np.maximum(0.0, (w + v) / 2), np.maximum(0.0, (w - v) / 2)], axis=1)
+        return multinomial_counts(probs, shots, seed, run)[:, 0]
+
 
 def without_classical_operations(circuit):
     """A copy of ``circuit`` without its measure instructions and classical bits (the reference's
@@ -341,21 +401,39 @@ class QiskitSamplingBackend(AQCBackend):
     "automatic" above 24 qubits, run the trajectories on the MPS engine instead
     (aqc_mps_traj_pair_tomo: every pair read from the trajectory's RDMs), at the simulator's learned
     capacity as its noisy shots do.  The concurrence lower bound stays noiseless-only.
+
+    ``pauli_terms``: how ``expectation_values_of_pauli_terms`` (and so
+    ``expectation_value_of_pauli_operator``) measures the terms of an operator with this backend.
+
+    * ``None``: the reference's route -- one rotated and measured copy of the circuit per term through
+      ``simulator.run``; under a noise model every copy is a full trajectory run;
+    * ``"device"`` (needs a simulator with ``pauli_counts``, i.e. a ``SamplingSimulator``): all terms
+      from one ``SamplingSimulator.pauli_counts`` call -- under a noise model ``shots`` trajectories,
+      each read out for every term (aqc_sv_traj_pauli_counts).  A term's estimate has the law of the
+      reference's circuit for that term; different terms share trajectories and are correlated.
+      Statevector trajectories only: the Pauli readout of MPS trajectories is not built.
     """
 
     TOMOGRAPHY_MODES = (None, "circuits", "device")
+    PAULI_TERMS_MODES = (None, "device")
 
-    def __init__(self, simulator=None, tomography=None, trajectory_tomography=False):
+    def __init__(self, simulator=None, tomography=None, trajectory_tomography=False, pauli_terms=None):
         if tomography not in self.TOMOGRAPHY_MODES:
             raise ValueError(f"tomography must be one of {self.TOMOGRAPHY_MODES}")
+        if pauli_terms not in self.PAULI_TERMS_MODES:
+            raise ValueError(f"pauli_terms must be one of {self.PAULI_TERMS_MODES}")
         if trajectory_tomography and tomography != "device":
             raise TypeError("trajectory_tomography=True needs tomography='device'")
         self.simulator = simulator if simulator is not None else SamplingSimulator()
         if tomography == "device" and not isinstance(self.simulator, SamplingSimulator):
             raise TypeError("tomography='device' needs a SamplingSimulator (its cached device state); "
                             "use tomography='circuits' with other simulators")
+        if pauli_terms == "device" and not callable(getattr(self.simulator, "pauli_counts", None)):
+            raise TypeError("pauli_terms='device' needs a simulator with pauli_counts (a SamplingSimulator); "
+                            "leave pauli_terms=None with other simulators")
         self.tomography = tomography
         self.trajectory_tomography = bool(trajectory_tomography)
+        self.pauli_terms = pauli_terms
 
     # -- pair tomography ---------------------------------------------------------------
     def _require_tomography(self):

@@ -43,6 +43,16 @@
 // POVM effects of the setting and draws one outcome by the multinomial rule.  The count tables are
 // integer sums (integer atomics): they do not depend on the launch shape either.
 //
+// The Pauli readout (aqc_sv_traj_pauli_counts) is a third ending: every trajectory serves every term.
+// Wave w takes terms w, w + nwaves, ...: its lanes stride over the 2^n amplitudes k and sum
+// conj(psi[k]) (M psi)[k] for the term's parity operator M, a product of one Hermitian 2x2 factor
+// D_q = E_q[+] - E_q[-] per qubit of its support.  The host folds the factors that are a multiple of a
+// Pauli into an x mask, a z mask and one complex scalar (one load per amplitude, whatever the weight)
+// and keeps the others -- at most 4: relaxation on the readout gives them an identity part -- as
+// general factors, 2^ng loads per amplitude.  A butterfly adds the lanes (no workgroup barrier, no LDS
+// beside the state), lane 0 clamps p_+ = (1 + v) / 2, draws one +-1 outcome and counts it (integer
+// atomics).  Term records are read from global memory at wave-uniform addresses.
+//
 // LDS layout: interleaved 16-byte complex amplitudes, as k_sv_segment's tile.  Split re / im arrays
 // (8-byte accesses) measured 2-7% slower at 8, 10, 12 and 13 qubits, with equal counts
 // (profiles/trajectory_layout_ab.json), and were removed.
@@ -70,8 +80,11 @@ constexpr size_t kMaxGlobalBytes = (size_t)512 << 20;
 
 enum { kGate1 = 0, kGate2 = 1, kKraus = 2, kKraus2 = 3 };
 enum { kLds = 0, kGlobal = 1 };
-enum { kEndDraw = 0, kEndPairs = 1 };  // a trajectory's ending: the full-register draw, or the pair readout
+// a trajectory's ending: the full-register draw, the pair readout, or the Pauli readout
+enum { kEndDraw = 0, kEndPairs = 1, kEndPaulis = 2 };
 constexpr int kMaxPairs = 4096;
+constexpr int kMaxTerms = 65536;
+constexpr int kMaxGeneral = 4;  // general (not Pauli-proportional) factors per term: 2^4 loads per amplitude
 
 // A program row as the kernel reads it.  Gate: m = the 2x2 / 4x4 matrix.  Kraus: m[8k ..] = K_k,
 // w[4k ..] = (M00, M11, Re M01, Im M01) of M = K_k^dag K_k, ev = the event index.  Kraus2 (one row per
@@ -85,6 +98,18 @@ struct TrajRow {
 static_assert(sizeof(TrajRow) == 416 && sizeof(TrajRow) % sizeof(double2) == 0, "TrajRow layout");
 constexpr int kRowWords = (int)(sizeof(TrajRow) / sizeof(double2));
 
+// A term of the Pauli readout as the kernel reads it: M = (cr + i ci) P (x) G, with P the Pauli string
+// whose entry (k, k ^ x) is (-1)^popcount(k & z) (X and Y qubits in x, Y and Z qubits in z; the scalars
+// of the factors and (-i)^ny folded into cr + i ci), and G the product of ng general factors, factor a
+// on qubit gq[a] as g[a] = (D00, D11, Re D01, Im D01).  The supports of P and G are disjoint.
+struct PauliTerm {
+  uint32_t x, z;
+  int32_t ng, gq[kMaxGeneral], pad;
+  double cr, ci;
+  double g[kMaxGeneral][4];
+};
+static_assert(sizeof(PauliTerm) == 176, "PauliTerm layout");
+
 struct TrajJob {
   const TrajRow* prog;
   int nprog, n, nshots, nev;
@@ -94,12 +119,25 @@ struct TrajJob {
   uint8_t* choices;  // null, or nshots x nev
   cplx* ws;          // kGlobal: 2^n amplitudes per workgroup
   int ustride;
-  // kEndPairs (nshots then counts trajectories, trajectory t serving setting t % 9)
-  int npairs;
-  const int* pairs;               // 2 npairs
-  const double* effects;          // [n][3][2][4]: (E00, E11, Re E01, Im E01)
-  unsigned long long* counts;     // [npairs][9][4]
-  uint8_t* outcomes;              // null, or nshots x npairs
+  // kEndPairs (nshots then counts trajectories, trajectory t serving setting t % 9); kEndPaulis (every
+  // trajectory serves every term) keeps its fields in the same storage, so TrajJob does not grow
+  union {
+    int npairs;
+    int nterms;
+  };
+  union {
+    const int* pairs;             // 2 npairs
+    const PauliTerm* terms;
+  };
+  union {
+    const double* effects;        // [n][3][2][4]: (E00, E11, Re E01, Im E01)
+    double* values;               // null, or nshots x nterms: v before clamping
+  };
+  union {
+    unsigned long long* counts;   // [npairs][9][4]
+    unsigned long long* plus;     // [nterms]: the outcome-0 draws
+  };
+  uint8_t* outcomes;              // null, or nshots x npairs / nshots x nterms
 };
 
 // bytes of dynamic LDS beside the state
@@ -140,6 +178,49 @@ __device__ __forceinline__ double wave_scan(double v, int lane) {
     if (lane >= d) v += t;
   }
   return v;
+}
+
+// One lane's share of sum_k conj(psi[k]) sign_z(k) sum_a (prod_f D_f[k_f, a_f]) psi[(k ^ x) with the bits
+// of the NG general factors set to a], k = lane, lane + 64, ...; the a loop unrolls, 2^NG loads.
+template <int MODE, int NG>
+__device__ __forceinline__ void pauli_term_sum(const Amps<MODE>& psi, const PauliTerm& tm, int lane, int dim, double& sx,
+                                               double& sy) {
+  const int x = (int)tm.x, z = (int)tm.z;
+  int q[NG > 0 ? NG : 1], gmask = 0;
+  double g[NG > 0 ? NG : 1][4];
+#pragma unroll
+  for (int f = 0; f < NG; ++f) {
+    q[f] = tm.gq[f];
+    gmask |= 1 << q[f];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) g[f][c] = tm.g[f][c];
+  }
+  for (int k = lane; k < dim; k += 64) {
+    const int base = (k ^ x) & ~gmask;
+    cplx row[NG > 0 ? NG : 1][2];  // row k_f of D_f
+#pragma unroll
+    for (int f = 0; f < NG; ++f) {
+      const bool kb = (k >> q[f]) & 1;  // D = (D00, D11, Re D01, Im D01); D10 = conj(D01)
+      row[f][0] = kb ? aqc::cmk(g[f][2], -g[f][3]) : aqc::cmk(g[f][0], 0.0);
+      row[f][1] = kb ? aqc::cmk(g[f][1], 0.0) : aqc::cmk(g[f][2], g[f][3]);
+    }
+    cplx acc = aqc::cmk(0.0, 0.0);
+#pragma unroll
+    for (int a = 0; a < (1 << NG); ++a) {
+      int idx = base;
+      cplx w = aqc::cmk(1.0, 0.0);
+#pragma unroll
+      for (int f = NG - 1; f >= 0; --f) {  // (the high factors first: their products are shared between a's)
+        idx |= ((a >> f) & 1) << q[f];
+        w = f == NG - 1 ? row[f][(a >> f) & 1] : aqc::cmul(w, row[f][(a >> f) & 1]);
+      }
+      acc = NG == 0 ? psi.ld(idx) : aqc::cfma(w, psi.ld(idx), acc);
+    }
+    const cplx t = aqc::cmulc(acc, psi.ld(k));  // acc conj(psi[k])
+    const double sg = (__popc(k & z) & 1) ? -1.0 : 1.0;
+    sx += sg * t.x;
+    sy += sg * t.y;
+  }
 }
 
 template <int MODE, int END, bool K2>
@@ -358,7 +439,32 @@ __global__ __launch_bounds__(kMaxThreads) void k_sv_traj(const TrajJob j) {
       }
     }
     __syncthreads();
-    if constexpr (END == kEndPairs) {
+    if constexpr (END == kEndPaulis) {
+      // ---- the Pauli readout: a wave per term, every term from every trajectory ----
+      for (int tj = wave; tj < j.nterms; tj += nwaves) {
+        const PauliTerm& tm = j.terms[tj];  // (wave-uniform address)
+        double sx = 0.0, sy = 0.0;
+        switch (tm.ng) {  // (wave-uniform: the general factors' loops unroll per count)
+          case 0: pauli_term_sum<MODE, 0>(psi, tm, lane, dim, sx, sy); break;
+          case 1: pauli_term_sum<MODE, 1>(psi, tm, lane, dim, sx, sy); break;
+          case 2: pauli_term_sum<MODE, 2>(psi, tm, lane, dim, sx, sy); break;
+          case 3: pauli_term_sum<MODE, 3>(psi, tm, lane, dim, sx, sy); break;
+          default: pauli_term_sum<MODE, 4>(psi, tm, lane, dim, sx, sy); break;
+        }
+        sx = wave_sum(sx);
+        sy = wave_sum(sy);
+        if (lane == 0) {
+          const double v = tm.cr * sx - tm.ci * sy;
+          const double pp = fmin(1.0, fmax(0.0, 0.5 * (1.0 + v)));
+          const double uu = j.u ? j.u[(size_t)shot * j.ustride + nev + tj]
+                                : aqc::sample_uniform(j.seed, j.run, (uint64_t)shot, (uint32_t)(nev + tj));
+          const int o = uu >= pp ? 1 : 0;
+          if (j.values) j.values[(size_t)shot * j.nterms + tj] = v;
+          if (j.outcomes) j.outcomes[(size_t)shot * j.nterms + tj] = (uint8_t)o;
+          if (!o) atomicAdd(j.plus + tj, 1ULL);
+        }
+      }
+    } else if constexpr (END == kEndPairs) {
       // ---- the pair readout: a wave per pair, setting s = shot % 9 ----
       const int s9 = shot % 9;
       for (int pj = wave; pj < j.npairs; pj += nwaves) {
@@ -734,6 +840,133 @@ extern "C" int aqc_sv_traj_pair_tomo(int n, const aqc_op_t* prog, int nprog, con
   AQC_HIP_CHECK(hipMemcpyAsync(counts, j.counts, (size_t)npairs * 36 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
   if (outcomes)
     AQC_HIP_CHECK(hipMemcpyAsync(outcomes, j.outcomes, (size_t)ntraj * npairs, hipMemcpyDeviceToHost, st));
+  AQC_HIP_CHECK(hipStreamSynchronize(st));
+  return AQC_OK;
+}
+
+namespace {
+
+// The term records of the Pauli readout from the codes (nterms x n; 0 I, 1 X, 2 Y, 3 Z) and the effects:
+// per qubit of a term's support D = E[q][c-1][0] - E[q][c-1][1]; a D that is a multiple of a Pauli
+// matrix within 1e-14, entry by entry, goes into the masks and the scalar, any other into the general
+// factors.
+int build_terms(int n, const uint8_t* codes, int nterms, const double* effects, std::vector<PauliTerm>& terms) {
+  constexpr double tol = 1e-14;
+  terms.assign((size_t)nterms, PauliTerm());
+  for (int t = 0; t < nterms; ++t) {
+    PauliTerm& tm = terms[t];
+    std::memset(&tm, 0, sizeof(tm));
+    double scal = 1.0;
+    int ny = 0, weight = 0;
+    for (int q = 0; q < n; ++q) {
+      const int c = codes[(size_t)t * n + q];
+      if (c > 3) return fail("a Pauli code must be 0 (I), 1 (X), 2 (Y) or 3 (Z)");
+      if (c == 0) continue;
+      ++weight;
+      const double* e0 = effects + (size_t)((q * 3 + c - 1) * 2) * 4;
+      double d[4];
+      for (int i = 0; i < 4; ++i) d[i] = e0[i] - e0[4 + i];
+      const bool diag0 = std::fabs(d[0]) <= tol && std::fabs(d[1]) <= tol;
+      if (diag0 && std::fabs(d[3]) <= tol) {  // d[2] X
+        scal *= d[2];
+        tm.x |= 1u << q;
+      } else if (diag0 && std::fabs(d[2]) <= tol) {  // -d[3] Y: Y01 = -i
+        scal *= -d[3];
+        tm.x |= 1u << q;
+        tm.z |= 1u << q;
+        ++ny;
+      } else if (std::fabs(d[0] + d[1]) <= tol && std::fabs(d[2]) <= tol && std::fabs(d[3]) <= tol) {  // d[0] Z
+        scal *= d[0];
+        tm.z |= 1u << q;
+      } else {
+        if (tm.ng == kMaxGeneral)
+          return fail("a term has more than 4 factors that are not a multiple of a Pauli matrix (the limit of "
+                      "general factors per term is 4)");
+        tm.gq[tm.ng] = q;
+        std::memcpy(tm.g[tm.ng], d, sizeof(d));
+        ++tm.ng;
+      }
+    }
+    if (weight == 0) return fail("an all-identity term (its value is 1: the caller answers it)");
+    // (-i)^ny: entry (k, k ^ 1) of Y is -i (-1)^k
+    static const double ph[4][2] = {{1.0, 0.0}, {0.0, -1.0}, {-1.0, 0.0}, {0.0, 1.0}};
+    tm.cr = scal * ph[ny & 3][0];
+    tm.ci = scal * ph[ny & 3][1];
+  }
+  return AQC_OK;
+}
+
+}  // namespace
+
+extern "C" int aqc_sv_traj_pauli_counts(int n, const aqc_op_t* prog, int nprog, const uint8_t* codes, int nterms,
+                                        const double* effects, int nshots, uint64_t seed, uint64_t run, const double* u,
+                                        int64_t* plus, double* values, uint8_t* outcomes) {
+  t_entry = "aqc_sv_traj_pauli_counts";
+  AQC_REQUIRE(plus && codes && effects && nprog >= 0 && (prog || nprog == 0), "aqc_sv_traj_pauli_counts: null argument");
+  AQC_REQUIRE(n >= 1 && n <= kMaxQubits, "aqc_sv_traj_pauli_counts: n must be in 1 .. 24");
+  AQC_REQUIRE(nterms >= 1 && nterms <= kMaxTerms, "aqc_sv_traj_pauli_counts: nterms must be in 1 .. 65536");
+  AQC_REQUIRE(nshots >= 1 && nshots <= kMaxShots, "aqc_sv_traj_pauli_counts: nshots must be in 1 .. 2^30");
+  if (int rc = aqc::check_effects(n, effects, t_entry)) return rc;
+  std::vector<PauliTerm> terms;
+  if (int rc = build_terms(n, codes, nterms, effects, terms)) return rc;
+  std::vector<TrajRow> rows;
+  int nev = 0;
+  if (int rc = build_rows(n, prog, nprog, rows, &nev)) return rc;
+  const bool k2 = std::any_of(rows.begin(), rows.end(), [](const TrajRow& r) { return r.kind == kKraus2; });
+  const int ustride = nev + nterms;
+  const size_t nu = (size_t)nshots * ustride;
+  if (u)
+    for (size_t e = 0; e < nu; ++e)
+      if (!(u[e] >= 0.0 && u[e] < 1.0)) return fail("u must lie in [0, 1)");
+  const size_t dim = (size_t)1 << n;
+  const bool in_lds = n <= kLdsMaxQubits;
+  const int threads = threads_for(n);
+  int grid = 0;
+  if (int rc = grid_for(n, nshots, threads, k2, &grid)) return rc;
+  const size_t nout = (size_t)nshots * nterms;
+  const size_t pb = up256(std::max<size_t>(1, rows.size()) * sizeof(TrajRow));
+  const size_t ub = u ? up256(nu * sizeof(double)) : 0;
+  const size_t tb = up256((size_t)nterms * sizeof(PauliTerm));
+  const size_t cb = up256((size_t)nterms * sizeof(int64_t));
+  const size_t vb = values ? up256(nout * sizeof(double)) : 0;
+  const size_t ob = outcomes ? up256(nout) : 0;
+  const size_t wb = in_lds ? 0 : (size_t)grid * dim * sizeof(cplx);
+  hipStream_t st = nullptr;
+  AQC_HIP_CHECK(hipDeviceSynchronize());  // (the scratch may be regrown)
+  aqc::DevScratch& sc = g_scr.here();
+  if (int rc = sc.ensure(pb + ub + tb + cb + vb + ob + wb)) return rc;
+  char* buf = sc.dev;
+  TrajJob j;
+  std::memset(&j, 0, sizeof(j));
+  j.prog = (const TrajRow*)buf;
+  j.nprog = nprog;
+  j.n = n;
+  j.nshots = nshots;
+  j.nev = nev;
+  j.ustride = ustride;
+  j.u = u ? (const double*)(buf + pb) : nullptr;
+  j.seed = seed;
+  j.run = run;
+  j.nterms = nterms;
+  j.terms = (const PauliTerm*)(buf + pb + ub);
+  j.plus = (unsigned long long*)(buf + pb + ub + tb);
+  j.values = values ? (double*)(buf + pb + ub + tb + cb) : nullptr;
+  j.outcomes = outcomes ? (uint8_t*)(buf + pb + ub + tb + cb + vb) : nullptr;
+  j.ws = in_lds ? nullptr : (cplx*)(buf + pb + ub + tb + cb + vb + ob);
+  if (!rows.empty())
+    AQC_HIP_CHECK(hipMemcpyAsync(buf, rows.data(), rows.size() * sizeof(TrajRow), hipMemcpyHostToDevice, st));
+  if (u) AQC_HIP_CHECK(hipMemcpyAsync(buf + pb, u, nu * sizeof(double), hipMemcpyHostToDevice, st));
+  AQC_HIP_CHECK(hipMemcpyAsync((void*)j.terms, terms.data(), (size_t)nterms * sizeof(PauliTerm), hipMemcpyHostToDevice, st));
+  AQC_HIP_CHECK(hipMemsetAsync(j.plus, 0, (size_t)nterms * sizeof(int64_t), st));
+  aqc::KernelTimer::begin(st, "sv_traj_pauli_counts", 0.0,
+                          (double)nshots * ((double)nprog * 14.0 + (double)nterms * 12.0) * (double)dim);
+  const int rc = launch<kEndPaulis>(j, grid, threads, in_lds, k2);
+  aqc::KernelTimer::end(st);
+  if (rc != AQC_OK) return rc;
+  AQC_CHECK_LAUNCH();
+  AQC_HIP_CHECK(hipMemcpyAsync(plus, j.plus, (size_t)nterms * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  if (values) AQC_HIP_CHECK(hipMemcpyAsync(values, j.values, nout * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (outcomes) AQC_HIP_CHECK(hipMemcpyAsync(outcomes, j.outcomes, nout, hipMemcpyDeviceToHost, st));
   AQC_HIP_CHECK(hipStreamSynchronize(st));
   return AQC_OK;
 }

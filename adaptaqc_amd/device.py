@@ -337,6 +337,42 @@ def trajectory_pair_tomography(n, rows, n_events, pairs, effects, shots, seed, r
     return (counts, outcomes) if return_outcomes else counts
 
 
+def trajectory_pauli_counts(n, rows, n_events, terms, effects, shots, seed, run=0, u=None, return_values=False,
+                            return_outcomes=False):
+    """The noisy Pauli readout of every term in one launch (aqc_sv_traj_pauli_counts): int64 [nterms], the
+    number of +1 parities among ``shots`` trajectories of the program ``rows`` (noise.trajectory_program
+    of the circuit without its classical operations, ``n_events`` events), every trajectory drawing one
+    +-1 outcome per term from its own state under the POVM ``effects`` [n, 3, 2, 4]
+    (noise.readout_effects).  ``terms``: qiskit labels (rightmost character = qubit 0) or an
+    (nterms, n) uint8 code array; no all-identity term.  The estimate of a term is
+    (2 plus - shots) / shots.  ``u``: [shots, n_events + nterms] uniforms in [0, 1) used instead of the
+    generator's (events first, then terms).  With ``return_values`` also the float64 [shots, nterms]
+    Re <psi_t|M_j|psi_t> before clamping, with ``return_outcomes`` the uint8 [shots, nterms] outcomes
+    (1 = parity -1); the result is then the tuple (plus[, values][, outcomes])."""
+    from . import paulis
+
+    n, shots, n_events = int(n), int(shots), int(n_events)
+    rows = np.ascontiguousarray(rows, dtype=_lib.OP_DTYPE)
+    if _count_events(rows) != n_events:
+        raise ValueError("trajectory_pauli_counts: n_events does not match the program's Kraus rows")
+    codes = paulis.terms_to_codes(terms, n)
+    nterms = len(codes)
+    eff = np.ascontiguousarray(effects, dtype=np.float64)
+    if eff.shape != (n, 3, 2, 4):
+        raise ValueError(f"trajectory_pauli_counts: effects must have shape {(n, 3, 2, 4)}")
+    up = _uniforms_arg(u, (shots, n_events + nterms))
+    plus = np.zeros(nterms, dtype=np.int64)
+    values = np.zeros((max(shots, 0), nterms)) if return_values else None
+    outcomes = np.zeros((max(shots, 0), nterms), dtype=np.uint8) if return_outcomes else None
+    _lib.check(_lib.lib().aqc_sv_traj_pauli_counts(n, _lib.ptr(rows) if len(rows) else None, len(rows),
+                                                   _lib.ptr(codes) if nterms else None, nterms, _lib.ptr(eff), shots,
+                                                   _u64(seed), _u64(run), _lib.ptr(up), _lib.ptr(plus),
+                                                   _lib.ptr(values) if return_values and nterms else None,
+                                                   _lib.ptr(outcomes) if return_outcomes and nterms else None))
+    out = (plus,) + ((values,) if return_values else ()) + ((outcomes,) if return_outcomes else ())
+    return out if len(out) > 1 else plus
+
+
 def mps_trajectory_sample(n, rows, n_events, shots, seed, run=0, u=None, return_choices=False, chi_cap=64,
                           threshold=1e-16, max_chi=None):
     """``shots`` noisy shots as quantum trajectories on the MPS engine (aqc_mps_traj_sample):

@@ -288,7 +288,10 @@ def expectation_values_of_pauli_terms(circuit, labels, backend, backend_options=
       state, not divided by <psi|psi>);
     * ``QiskitSamplingBackend``: per term a copy of the circuit with the reference's basis rotations
       and a measure on every qubit, counts from ``backend.simulator.run(copy, **execute_kwargs)``
-      (``shots``, ``seed_simulator``), then the parity average.
+      (``shots``, ``seed_simulator``), then the parity average.  A backend built with
+      ``pauli_terms="device"`` hands all non-identity terms to one
+      ``backend.simulator.pauli_counts`` call instead (under a noise model: ``shots`` trajectories,
+      each read out for every term); a term's value is (2 plus - shots) / shots.
 
     ``circuit`` is not modified (its own measure instructions are ignored); ``backend_options`` are
     Aer's and have no meaning here."""
@@ -315,6 +318,13 @@ def expectation_values_of_pauli_terms(circuit, labels, backend, backend_options=
         out[todo] = backend.device_state(circuit).pauli_expect(codes[todo])
     elif isinstance(backend, QiskitSamplingBackend):
         kwargs = dict(execute_kwargs or {})
+        if getattr(backend, "pauli_terms", None) == "device":
+            shots = int(kwargs.get("shots", 1024))
+            plus = backend.simulator.pauli_counts(circuit, [labels[t] for t in todo], shots=shots,
+                                                  seed_simulator=kwargs.get("seed_simulator"),
+                                                  noise_model=kwargs.get("noise_model"))
+            out[todo] = (2.0 * np.asarray(plus, dtype=float) - shots) / shots
+            return out
         for t in todo:
             rotated = circuit.copy()
             rotated.data = [ins for ins in rotated.data if ins.operation.name != "measure"]

@@ -216,6 +216,38 @@ int aqc_sv_traj_sample(int n, const aqc_op_t* prog, int nprog, int nshots, uint6
 int aqc_sv_traj_pair_tomo(int n, const aqc_op_t* prog, int nprog, const int* pairs, int npairs, const double* effects,
                           int nshots, uint64_t seed, uint64_t run, const double* u, int64_t* counts, uint8_t* outcomes);
 
+/* ---- noisy Pauli readout: every term of an operator from each trajectory -------------------------
+   What the reference measures when expectation_value_of_pauli_operator runs one rotated circuit per
+   term under a NoiseModel (circuit_operations_pauli_ops.py:71-103), as one launch of nshots
+   trajectories.  prog, effects: as aqc_sv_traj_pair_tomo (same validation, same event numbering, E
+   events).  codes: nterms x n bytes, codes[j n + q] = c_q of term j: 0 I, 1 X, 2 Y, 3 Z.
+   The parity operator of a term: for each qubit q of its support S (c_q != 0),
+   D_q = E[q][c_q - 1][0] - E[q][c_q - 1][1], a Hermitian 2x2 matrix; M = (x)_{q in S} D_q with the
+   identity elsewhere.  (A noisy measure on a qubit outside S drops out: its two effects sum to I.
+   D_q need not be a multiple of a Pauli matrix: relaxation on measure gives E0 = diag(1, g),
+   E1 = diag(0, 1 - g), so D has an identity part.)
+   Trajectory t runs the rows as in aqc_sv_traj_sample; then for EVERY term j: v = Re <psi_t|M_j|psi_t>,
+   p+ = min(1, max(0, (1 + v) / 2)), and the outcome is 1 (parity -1) iff u >= p+, with
+   u = sample_uniform(seed, run, t, E + j); when u is not NULL, u[t (E + nterms) + E + j], host doubles
+   in [0, 1), events first, then terms.  One trajectory and one draw is one shot of the reference's
+   circuit for that term, so plus[j] has the reference's law; different terms share trajectories and
+   are correlated.
+   plus[j]: host int64, the number of outcome-0 draws (the estimate is (2 plus - nshots) / nshots).
+   values: NULL, or nshots x nterms doubles, v before clamping.  outcomes: NULL, or nshots x nterms
+   bytes.  An outcome depends on (seed, run, t) only: fewer shots give a prefix.  Every floating-point
+   sum runs in a fixed order and plus accumulates by integer atomics: two calls return the same bits.
+   A factor D_q that is c sigma for a Pauli matrix sigma within 1e-14, entry by entry (noiseless
+   readout, unital readout noise), costs nothing per amplitude, at any weight; a term may hold at most
+   4 other ("general") factors, each doubling the loads per amplitude.
+   State placement as aqc_sv_traj_sample.
+   AQC_ERR_ARG, before any device call: as aqc_sv_traj_sample and the effects check of
+   aqc_sv_traj_pair_tomo; n outside 1 .. 24, nterms outside 1 .. 65536, nshots outside 1 .. 2^30, a
+   code above 3, an all-identity term (its value is 1: the caller answers it), a term with more than
+   4 general factors. */
+int aqc_sv_traj_pauli_counts(int n, const aqc_op_t* prog, int nprog, const uint8_t* codes, int nterms,
+                             const double* effects, int nshots, uint64_t seed, uint64_t run, const double* u,
+                             int64_t* plus, double* values, uint8_t* outcomes);
+
 /* ---- noisy shot sampling above 24 qubits: quantum trajectories on the MPS engine -----------------
    (Aer's qasm_simulator with method="matrix_product_state" under a NoiseModel.)
    prog: aqc_sv_traj_sample's program.  Per shot: an MPS |0...0> of capacity chi_cap with the
