@@ -91,6 +91,15 @@ constexpr double kJacobiNoise = 0.0;
 // Fused per-state chain (k_chain) for batches of >= g_chain_min_states states at 2 chi = 128
 // (aqc_mps_set_fused_chain: 0 off, 1 from 32 states, 2 from one state).
 bool g_fused_chain = true;
+// What the Gram body does itself for an update of the chain (aqc_mps_set_chain_epilogue): 0 nothing
+// (rank_body and split_copy_body run), 1 the rank decision, 2 the rank and the copied site.
+// The initial value from AQC_CHAIN_EPILOGUE (A/B runs of the benchmark), default 1: on the bench 2
+// was not faster than 1 in every run (profiles/chain_epilogue_ab.json).
+int g_chain_epilogue = [] {
+  const char* e = std::getenv("AQC_CHAIN_EPILOGUE");
+  const int v = e ? std::atoi(e) : 1;
+  return v >= 0 && v <= 2 ? v : 1;
+}();
 int g_chain_min_states = 32;
 // dynamic LDS of the 1024-thread two-site kernels: four 64 x 64 GEMM tiles (>= the register
 // Jacobi's 64 x 129 complex exchange buffer)
@@ -844,28 +853,12 @@ __device__ __forceinline__ void rank_body(const TwoSiteJob& j) {
     }
   }
   if (tid == 0) {
-    int k = 0;
-    for (int i = 0; i < C; ++i)
-      if (sv[i] * sv[i] > kChop) ++k;
-    if (k < 1) k = 1;
-    if (j.max_chi > 0 && k > j.max_chi) k = j.max_chi;
     // (a Gram path that decided the kept count hands over the tail it removed: sig[kSigTail])
-    double tail = aqc::ldg(j.sig + kSigTail);
-    while (k > 1 && tail + sv[k - 1] * sv[k - 1] < j.thr) {
-      tail += sv[k - 1] * sv[k - 1];
-      --k;
-    }
+    double nrm;
+    const int k = rank_rule(j, sv, C, aqc::ldg(j.sig + kSigTail), nrm);
     aqc::stg(j.sig + kSigTail, 0.0);
-    // the bond capacity is this library's limit, not Aer's: only a kept count above it (after the
-    // whole reduce_zeros rule) overflows
-    if (k > j.cap) {
-      k = j.cap;
-      atomicOr(&j.flags[0], 1);
-    }
-    double nn = 0.0;
-    for (int i = 0; i < k; ++i) nn += sv[i] * sv[i];
     kk_s = k;
-    norm_s = sqrt(nn);
+    norm_s = nrm;
     *(__attribute__((address_space(1))) int*)(j.dims + 1) = k;
   }
   __syncthreads();
@@ -1237,14 +1230,18 @@ __device__ __forceinline__ void chain_theta_mfma(const TwoSiteJob& j) {
 // the register Jacobi is the chain's fallback (Gram path off or refused): a real call, so that
 // its register allocation stays out of k_chain's
 __device__ __noinline__ void chain_jacobi_fallback(const TwoSiteJob& j) { jacobi_reg_body<128, 8, 16>(j); }
-__device__ __forceinline__ void chain_jacobi(const TwoSiteJob& j) {
+// Returns what the Gram body's epilogue (epi, aqc_mps_set_chain_epilogue) has already done for
+// this update: 0 nothing, 1 the rank, 2 the rank and the copied site.
+__device__ __forceinline__ int chain_jacobi(const TwoSiteJob& j, int epi) {
   if (j.gram) {
-    const int g = gram_svd_body(j);
-    if (g == 1) return;
+    const int g = gram_svd_body(j, epi);
+    if (g == 1) return 0;
+    if (g > 2) return g - 2;
     __syncthreads();
-    if (g == 2 && gram_certified(j)) return;
+    if (g == 2 && gram_certified(j)) return 0;
   }
   chain_jacobi_fallback(j);
+  return 0;
 }
 __device__ __forceinline__ void chain_rank(const TwoSiteJob& j) { rank_body<1024, 128>(j); }
 // The split GEMM in the chain: its output (k x N, or M x k) is two 64 x 64 blocks, so the four
@@ -1323,14 +1320,15 @@ __device__ __forceinline__ void split_gemm_chain(const TwoSiteJob& j, int tid) {
         }
   }
 }
-__device__ __forceinline__ void chain_split(const TwoSiteJob& j) {
+// (copied: the Gram body's epilogue has already written the copied site)
+__device__ __forceinline__ void chain_split(const TwoSiteJob& j, bool copied) {
   const int tid = fresh_tid();
-  split_copy_body(j, tid, 1024);
+  if (!copied) split_copy_body(j, tid, 1024);
   split_gemm_chain(j, tid);
 }
 
 __global__ __launch_bounds__(1024) void k_chain(const ChainJob* __restrict__ chains, const TwoSiteJob* __restrict__ two,
-                                                const OneSiteJob* __restrict__ one) {
+                                                const OneSiteJob* __restrict__ one, int epi) {
   const ChainJob& c = chains[blockIdx.x];
   const int tid = fresh_tid();
   // shader-clock ticks of the phases (thread 0 of each workgroup; aqc_mps_chain_ticks), kept in
@@ -1362,13 +1360,13 @@ __global__ __launch_bounds__(1024) void k_chain(const ChainJob* __restrict__ cha
 #endif
     __syncthreads();
     tick(0);
-    chain_jacobi(j);
+    const int done = __builtin_amdgcn_readfirstlane(chain_jacobi(j, epi));  // (uniform: an SGPR)
     __syncthreads();
     tick(1);
-    chain_rank(j);
+    if (done == 0) chain_rank(j);
     __syncthreads();
     tick(2);
-    chain_split(j);
+    chain_split(j, done == 2);
     __syncthreads();
     tick(3);
   }
@@ -1589,7 +1587,7 @@ int run_chains(aqc_mps_t* hs, int ns, std::vector<std::vector<DevOp>>& lists, in
   // algorithmic: the two sites' Gammas in and out; nominal SVD + theta + split flops
   aqc::KernelTimer::begin(st, "mps_chain", nj * 8.0 * c * c * 16, nj * (84.0 * 8.0 + 64.0) * c * c * c);
   hipLaunchKernelGGL(k_chain, dim3(ns), dim3(1024), kChainLds, st, (const ChainJob*)(db + o_chain),
-                     (const TwoSiteJob*)(db + o_two), (const OneSiteJob*)(db + o_one));
+                     (const TwoSiteJob*)(db + o_two), (const OneSiteJob*)(db + o_one), g_chain_epilogue);
   aqc::KernelTimer::end(st);
   AQC_CHECK_LAUNCH();
   return AQC_OK;  // the lease records the set's event
@@ -2108,6 +2106,23 @@ int aqc_mps_chain_ticks(double* out) {
   const unsigned long long z[5] = {0, 0, 0, 0, 0};
   AQC_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_chain_ticks), z, sizeof(z)));
   for (int i = 0; i < 5; ++i) out[i] = (double)t[i];
+  return AQC_OK;
+}
+
+int aqc_mps_set_chain_epilogue(int mode) {
+  AQC_REQUIRE(mode >= 0 && mode <= 2, "aqc_mps_set_chain_epilogue: 0, 1 or 2");
+  g_chain_epilogue = mode;
+  return AQC_OK;
+}
+
+int aqc_mps_chain_epilogue_stats(double* out) {
+  AQC_REQUIRE(out, "aqc_mps_chain_epilogue_stats: null argument");
+  unsigned long long t[2] = {0, 0};
+  AQC_HIP_CHECK(hipStreamSynchronize(aqc::mps_stream()));
+  AQC_HIP_CHECK(hipMemcpyFromSymbol(t, HIP_SYMBOL(g_epi_stats), sizeof(t)));
+  const unsigned long long z[2] = {0, 0};
+  AQC_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_epi_stats), z, sizeof(z)));
+  for (int i = 0; i < 2; ++i) out[i] = (double)t[i];
   return AQC_OK;
 }
 

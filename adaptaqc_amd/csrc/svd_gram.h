@@ -57,6 +57,35 @@ static_assert(kGramNarrowK == 64, "S5: the narrow inverse iteration (tid < K) st
 // path counters (thread 0 of each call): [0] calls, [1] taken, [2] declined by shape (K > 64, ...),
 // [3] declined at the eigenvalue floor (lambda_K <= 1e-9 lambda_1 -> the Jacobi runs)
 __device__ unsigned long long g_gram_stats[6];  // calls, taken, declined (shape), declined (decision / floor), certificates, certified
+// the fused chain's epilogue inside the body (aqc_mps_set_chain_epilogue): [0] updates whose rank was
+// decided here, [1] updates handed back to rank_body because sigma came out of S5 unsorted
+__device__ unsigned long long g_epi_stats[2];
+
+// reduce_zeros on the sorted singular values sv[0, n) (any past n are zero; thread 0 only), seeded
+// with the tail a Gram path already dropped: the CHOP count, the max_chi cap, the tail rule and the
+// capacity check (flag 1 on overflow).  Returns the kept count, the kept values' norm in `norm`.
+// One body for rank_body and for the Gram body's own epilogue, so that both contract alike.
+__device__ __forceinline__ int rank_rule(const TwoSiteJob& j, const double* sv, int n, double tail, double& norm) {
+  int k = 0;
+  for (int i = 0; i < n; ++i)
+    if (sv[i] * sv[i] > kChop) ++k;
+  if (k < 1) k = 1;
+  if (j.max_chi > 0 && k > j.max_chi) k = j.max_chi;
+  while (k > 1 && tail + sv[k - 1] * sv[k - 1] < j.thr) {
+    tail += sv[k - 1] * sv[k - 1];
+    --k;
+  }
+  // the bond capacity is this library's limit, not Aer's: only a kept count above it (after the
+  // whole reduce_zeros rule) overflows
+  if (k > j.cap) {
+    k = j.cap;
+    atomicOr(&j.flags[0], 1);
+  }
+  double nn = 0.0;
+  for (int i = 0; i < k; ++i) nn += sv[i] * sv[i];
+  norm = sqrt(nn);
+  return k;
+}
 
 // Sum over the 64 lanes, result uniform: DPP row sums, then the four rows through readlane (no
 // LDS crossbar; every lane must be active).
@@ -357,7 +386,7 @@ __device__ __forceinline__ double rayleigh(int i, int C, const double* zb, const
 // = V sigma into the work buffer.  Every thread of the workgroup.
 __device__ __forceinline__ void s6_back(const TwoSiteJob& j, cplx* hh, int C, int K, int c0, aqc::d4_t (&vre)[2],
                                         aqc::d4_t (&vim)[2], const double* s_sig2, int tid, int lane, int wave,
-                                        int wave_s) {
+                                        int wave_s, bool copy = false, bool gtr = false, const int* s_fk = nullptr) {
   extern __shared__ double2 xbuf[];
   const int nt = wave & 3, mg = wave >> 2, li = lane & 15, lk = lane >> 4;
   // LDS (complex units): Y [128][16] (column index swizzled by row & 15: conflict-free reads along
@@ -490,6 +519,30 @@ __device__ __forceinline__ void s6_back(const TwoSiteJob& j, cplx* hh, int C, in
         for (int q = 0; q < 4; ++q) {
           const int row = 32 * mg + 16 * t + lk + 4 * q;
           if (row < C) aqc::stg(j.work + (size_t)col * C + row, aqc::cmk(vre[t][q] * sg, vim[t][q] * sg));
+        }
+      }
+    }
+    // the chain's epilogue: the copied site's Gamma (split_copy_body's, on its qr = 1 side: W's
+    // columns have length C) from the same W, for the *s_fk columns the rank rule kept
+    if (copy && col < *s_fk) {  // (*s_fk: written before this call's first barrier)
+      const int chs = C >> 1;  // the copied site's outer bond: chr (Gq') if !gtr, chl (Gp') if gtr
+      const size_t half = (size_t)j.cap * j.cap;
+      const double sg = sqrt(s_sig2[col]);
+      const double* lo = gtr ? j.ll : j.lr;
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int row = 32 * mg + 16 * t + lk + 4 * q;
+          if (row < C) {
+            const int s = row >= chs, o = row - s * chs;
+            const double d = sg * aqc::ldg(lo + o);
+            cplx w = aqc::cmk(vre[t][q] * sg, vim[t][q] * sg);
+            if (!gtr) w = aqc::cconj(w);
+            w = d != 0.0 ? aqc::cscale(w, 1.0 / d) : aqc::cmk(0, 0);
+            if (gtr) aqc::stg(j.gp + s * half + (size_t)o * j.cap + col, w);  // Gp'[s1][l][kk]
+            else aqc::stg(j.gq + s * half + (size_t)col * j.cap + o, w);      // Gq'[s2][kk][r]
+          }
         }
       }
     }
@@ -851,10 +904,10 @@ __device__ __forceinline__
 #else
 __device__ __noinline__
 #endif
-int gram_svd_body(const TwoSiteJob& j) {
+int gram_svd_body(const TwoSiteJob& j, int epi) {
   extern __shared__ double2 xbuf[];
   __shared__ double s_d[128], s_e[128], s_e2[128], s_lam[128], s_err[128], s_sig2[kGramMaxK], s_tail;
-  __shared__ int s_K, s_cert;
+  __shared__ int s_K, s_cert, s_fk;
   __shared__ cplx s_tau[128];
   __shared__ double s_lo, s_hi, s_tn;
   __shared__ double2 s_de[128];
@@ -1517,18 +1570,50 @@ int gram_svd_body(const TwoSiteJob& j) {
       vim[t][q] = 0.0;
     }
   }
-  s6_back(j, hh, C, K, 0, vre, vim, s_sig2, tid, lane, wave, wave_s);
+  // ---- the fused chain's epilogue (epi: 1 the rank, 2 also the copied site; 0 from the lock-step
+  // kernel), for an update that will return 1: sigma is final here and comes out of S4 / S5 in
+  // descending order, so rank_body's sort is the identity unless two Rayleigh quotients of a
+  // cluster came out swapped.  Wave 0 checks that under rank_body's order (ties by index, so >=),
+  // thread 0 runs rank_rule on sigma in the LDS (s_err is dead since gram_keep) and the wave writes
+  // what rank_body writes; an unsorted sigma leaves the update to rank_body (s_fk = 0). ----
+  if (epi == 2 && j.qr == 0) epi = 1;  // (the copy below writes the qr = 1 side, the chain's)
+  if (epi && !s_cert && wave == 0) {  // (uniform per wave)
+    const double sg = lane < K ? sqrt(s_sig2[lane]) : 0.0;
+    s_err[lane] = sg;
+    const bool ok = __ballot(lane >= K - 1 || sg >= __shfl_down(sg, 1)) == ~0ull;
+    __builtin_amdgcn_wave_barrier();
+    double nrm = 0.0;
+    int k = 0;
+    if (lane == 0) {
+      if (ok) {
+        k = rank_rule(j, s_err, K, s_tail, nrm);
+        *(__attribute__((address_space(1))) int*)(j.dims + 1) = k;
+      }
+      s_fk = k;
+      atomicAdd(&g_epi_stats[ok ? 0 : 1], 1ull);
+    }
+    k = __builtin_amdgcn_readfirstlane(k);
+    nrm = uniform_d(nrm);
+    if (lane < k) {
+      aqc::stg(j.lm + lane, sg / nrm);
+      *(__attribute__((address_space(1))) int*)(j.perm + lane) = lane;
+      aqc::stg(j.sig + lane + kSigMax, sg);
+    }
+  }
+  s6_back(j, hh, C, K, 0, vre, vim, s_sig2, tid, lane, wave, wave_s, epi == 2 && !s_cert, tr, &s_fk);
   tick(4);
   }  // (K <= 64)
+  const int fk = (epi && !s_cert && K <= kGramNarrowK) ? __builtin_amdgcn_readfirstlane(s_fk) : 0;  // (uniform)
   for (int c = tid; c < C; c += 1024) aqc::stg(j.sig + c, c < K ? sqrt(s_sig2[c]) : 0.0);
-  if (tid == 0) aqc::stg(j.sig + kSigTail, s_tail);  // the tail gram_keep dropped (rank_body)
+  // the tail gram_keep dropped, for rank_body (which clears it, as the epilogue above has)
+  if (tid == 0) aqc::stg(j.sig + kSigTail, fk ? 0.0 : s_tail);
   tick(5);
   if (s_cert) return 2;  // (uniform) the caller runs gram_certified
   if (tid == 0) {
     atomicMax(&j.flags[2], 1);
     atomicAdd(&g_gram_stats[1], 1ull);
   }
-  return 1;
+  return fk ? 2 + epi : 1;  // 3: the rank is decided, 4: and the copied site written
 }
 
 // After gram_svd_body returned 2 (its kept count assumed the values in CHOP's error band chopped):
@@ -1566,7 +1651,7 @@ __device__ __noinline__ bool gram_certified(const TwoSiteJob& j) {
 
 __global__ __launch_bounds__(1024) void k_svd_gram(const TwoSiteJob* __restrict__ jobs) {
   const TwoSiteJob& j = jobs[blockIdx.x];
-  const int g = j.gram ? gram_svd_body(j) : 0;
+  const int g = j.gram ? gram_svd_body(j, 0) : 0;
   if (g == 1) return;
   __syncthreads();
   if (g == 2 && gram_certified(j)) return;

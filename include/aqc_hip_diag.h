@@ -105,6 +105,16 @@ int aqc_scratch_stats(double* out);
    updates); on = 0 selects the lock-step launches per update, on = 2 the fused chain for batches
    of any size (lab: single evaluations).  Default 1. */
 int aqc_mps_set_fused_chain(int on);
+/* What the fused chain's Gram SVD does itself for an update it takes on its narrow path (K <= 64, no
+   certificate), after checking that sigma left it sorted: mode 0 nothing (the chain's rank and copy
+   phases run), 1, the default, the rank decision (reduce_zeros, lambda, dims, the sorted sigma), 2
+   also the copied site's Gamma, written from the registers that hold V (AQC_CHAIN_EPILOGUE sets the
+   initial value).  Every other update keeps
+   the chain's own phases; the results are bit for bit those of mode 0. */
+int aqc_mps_set_chain_epilogue(int mode);
+/* Updates since the last call (then reset): out[0] whose rank the Gram SVD decided itself, out[1]
+   handed back to the chain's rank phase because sigma was not sorted; out[2]. */
+int aqc_mps_chain_epilogue_stats(double* out);
 /* Diagnostics: shader-clock ticks spent by the fused chain's workgroups (thread 0) in theta,
    Jacobi, rank, split and one-site ops since the last call (then reset); out[5]. */
 int aqc_mps_chain_ticks(double* out);
