@@ -42,7 +42,7 @@ EXPORTS = (
     "aqc_comm_unique_id", "aqc_comm_init", "aqc_comm_destroy", "aqc_comm_rank", "aqc_allgather_f64",
     "aqc_allgather_f64_host", "aqc_allreduce_max_f64", "aqc_svd_gram_big_stats", "aqc_svd_gram_big_ticks",
     "aqc_gb_set_spin_limit", "aqc_gb_set_tail", "aqc_gb_set_stages", "aqc_debug_hog", "aqc_pool_stats",
-    "aqc_scratch_stats", "aqc_mps_set_chain_epilogue", "aqc_mps_chain_epilogue_stats",
+    "aqc_scratch_stats", "aqc_mps_set_chain_epilogue", "aqc_mps_get_chain_epilogue", "aqc_mps_chain_epilogue_stats",
     "aqc_env_fallbacks", "aqc_env_set_single", "aqc_env_set_spin_limit",
     "aqc_sv_sample", "aqc_mps_sample", "aqc_sample_uniforms", "aqc_sv_traj_sample",
     "aqc_sv_traj_pair_tomo", "aqc_sv_traj_pauli_counts", "aqc_mps_traj_sample", "aqc_mps_traj_plan", "aqc_mps_traj_set_batch",
@@ -119,6 +119,7 @@ _SIGS = {
     "aqc_mps_set_fused_chain": ([_I], _I),
     "aqc_mps_chain_ticks": ([_P], _I),
     "aqc_mps_set_chain_epilogue": ([_I], _I),
+    "aqc_mps_get_chain_epilogue": ([], _I),
     "aqc_mps_chain_epilogue_stats": ([_P], _I),
     "aqc_svd_debug": ([_P, _I, _I, _I, _I, _P, _P, _P, _P], _I),
     "aqc_sv_pair_rdms": ([_P, _P, _I, _P], _I),

@@ -92,13 +92,15 @@ constexpr double kJacobiNoise = 0.0;
 // (aqc_mps_set_fused_chain: 0 off, 1 from 32 states, 2 from one state).
 bool g_fused_chain = true;
 // What the Gram body does itself for an update of the chain (aqc_mps_set_chain_epilogue): 0 nothing
-// (rank_body and split_copy_body run), 1 the rank decision, 2 the rank and the copied site.
-// The initial value from AQC_CHAIN_EPILOGUE (A/B runs of the benchmark), default 1: on the bench 2
-// was not faster than 1 in every run (profiles/chain_epilogue_ab.json).
+// (rank_body and split_copy_body run), 1 the rank decision, 2 the rank and the copied site, 3 the
+// rank decision, and S6 leaves V in the LDS for a split of its own (split_lds_chain).
+// The initial value from AQC_CHAIN_EPILOGUE (A/B runs of the benchmark), default 3: on the bench 2
+// was not faster than 1 in every run (profiles/chain_epilogue_ab.json),
+// and every run of 3 was below every run of 1 (profiles/chain_split_lds_ab.json; item 14).
 int g_chain_epilogue = [] {
   const char* e = std::getenv("AQC_CHAIN_EPILOGUE");
-  const int v = e ? std::atoi(e) : 1;
-  return v >= 0 && v <= 2 ? v : 1;
+  const int v = e ? std::atoi(e) : 3;
+  return v >= 0 && v <= 3 ? v : 3;
 }();
 int g_chain_min_states = 32;
 // dynamic LDS of the 1024-thread two-site kernels: four 64 x 64 GEMM tiles (>= the register
@@ -1231,7 +1233,8 @@ __device__ __forceinline__ void chain_theta_mfma(const TwoSiteJob& j) {
 // its register allocation stays out of k_chain's
 __device__ __noinline__ void chain_jacobi_fallback(const TwoSiteJob& j) { jacobi_reg_body<128, 8, 16>(j); }
 // Returns what the Gram body's epilogue (epi, aqc_mps_set_chain_epilogue) has already done for
-// this update: 0 nothing, 1 the rank, 2 the rank and the copied site.
+// this update: 0 nothing, 1 the rank, 2 the rank and the copied site, 3 the rank, with V left in
+// the dynamic LDS for split_lds_chain.
 __device__ __forceinline__ int chain_jacobi(const TwoSiteJob& j, int epi) {
   if (j.gram) {
     const int g = gram_svd_body(j, epi);
@@ -1320,10 +1323,124 @@ __device__ __forceinline__ void split_gemm_chain(const TwoSiteJob& j, int tid) {
         }
   }
 }
-// (copied: the Gram body's epilogue has already written the copied site)
-__device__ __forceinline__ void chain_split(const TwoSiteJob& j, bool copied) {
+// The split of an update whose Gram body left V (and the reciprocals of sigma, ll, lr) in the dynamic
+// LDS (chain epilogue 3, kVlPos in svd_gram.h; qr = 1, perm the identity, k <= 64 kept columns).
+// TR as in split_copy_body.  With W = V Sigma, split_copy_body's W / (sigma lambda) is V / lambda and
+// the GEMM's theta W / (sigma^2 lambda) is (theta V) / sigma / lambda:
+//    TR (M >= N): Gq'[s2][kk][r] = conj(V[s2 chr + r][kk]) / lr[r]   (copied),
+//                 Gp'[s1][l][kk] = sum_c theta[s1 chl + l][c] V[c][kk] / sigma_kk / ll[l]
+//   !TR (M <  N): Gp'[s1][l][kk] = V[s1 chl + l][kk] / ll[l]          (copied),
+//                 Gq'[s2][kk][r] = sum_R conj(V[R][kk]) theta[R][s2 chr + r] / sigma_kk / lr[r]
+// The copied site by all 1024 threads, lanes along the tensor's fastest index.  The GEMM's 128 x 64
+// (64 x 128) output is 32 tiles of 16 x 16, two per wave: wave w takes the 16 theta-side indices of
+// row tile w >> 1 against kept-column tiles 2 (w & 1) and 2 (w & 1) + 1, over the whole contraction
+// length C -- no partial sums to exchange, no barrier.  theta' goes from global memory straight into
+// the MFMA operand registers, two k-steps ahead of the products (TR: 16 lanes read a 256-byte run of
+// a column); V comes from the LDS.  Three real products per complex one (3M, as S1 and S6):
+//    TR: P1 = tr vr, P2 = ti vi, P3 = (tr + ti)(vr + vi): Re = P1 - P2, Im = P3 - P1 - P2
+//   !TR: (conj V) P3 = (vr - vi)(tr + ti):                 Re = P1 + P2, Im = P3 - P1 + P2
+// !TR puts V on the A side, so that in both orientations the accumulator's lanes li run along the
+// output tensor's fastest index (16 lanes store a 256-byte run).
+template <bool TR>
+__device__ __forceinline__ void split_lds_body(const TwoSiteJob& j, int tid) {
+  extern __shared__ double2 xbuf[];
+  const cplx* Vl = xbuf;
+  const double* rcp = reinterpret_cast<const double*>(xbuf + kVlElems);
+  const int chl = j.dims[0], k = j.dims[1], chr = j.dims[2];
+  const int M = 2 * chl, N = 2 * chr;
+  const int C = TR ? N : M;
+  const int cap = j.cap;
+  const size_t half = (size_t)cap * cap;
+  if (TR) {
+    for (int e = tid; e < N * k; e += 1024) {
+      const int cc = e % N, kk = e / N;
+      const int s2 = cc >= chr, r = cc - s2 * chr;
+      const double f = rcp[kVlRcpSig + kk] != 0.0 ? rcp[kVlRcpLr + r] : 0.0;
+      const cplx v = Vl[kVlPos(cc, kk)];
+      aqc::stg(j.gq + s2 * half + (size_t)kk * cap + r, aqc::cmk(v.x * f, -v.y * f));
+    }
+  } else {
+    for (int e = tid; e < M * k; e += 1024) {
+      const int kk = e % k, R = e / k;
+      const int s1 = R >= chl, l = R - s1 * chl;
+      const double f = rcp[kVlRcpSig + kk] != 0.0 ? rcp[kVlRcpLl + l] : 0.0;
+      const cplx v = Vl[kVlPos(R, kk)];
+      aqc::stg(j.gp + s1 * half + (size_t)l * cap + kk, aqc::cmk(v.x * f, v.y * f));
+    }
+  }
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const int li = lane & 15, lk = lane >> 4;
+  const int rt = wave >> 1, ct = 2 * (wave & 1);
+  const int outer = TR ? M : N;       // theta's other side: the GEMM site's (s, outer bond) index
+  if (16 * rt >= outer) return;       // (uniform per wave; nothing below synchronises)
+  const int m = 16 * rt + li;
+  const bool mok = m < outer;
+  // theta[R][c] = th[c * M + R]; this lane's element of k-step s is (m, 4 s + lk)
+  const cplx* tp = j.theta + (TR ? (size_t)lk * M + m : (size_t)m * M + lk);
+  const size_t ts = TR ? (size_t)4 * M : 4;
+  auto ldt = [&](int s) { return (mok && 4 * s + lk < C) ? aqc::ldg(tp + s * ts) : aqc::cmk(0, 0); };
+  aqc::d4_t p1[2], p2[2], p3[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) p1[u] = p2[u] = p3[u] = aqc::d4_t{0, 0, 0, 0};
+  auto kstep = [&](int s, cplx t) {
+    const int row = 4 * s + lk;  // (< 128: rows past C hold zeros, as t does)
+    const double tsum = t.x + t.y;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const cplx v = Vl[kVlPos(row, 16 * (ct + u) + li)];
+      if (TR) {
+        p1[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(t.x, v.x, p1[u], 0, 0, 0);
+        p2[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(t.y, v.y, p2[u], 0, 0, 0);
+        p3[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(tsum, v.x + v.y, p3[u], 0, 0, 0);
+      } else {
+        p1[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(v.x, t.x, p1[u], 0, 0, 0);
+        p2[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(v.y, t.y, p2[u], 0, 0, 0);
+        p3[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(v.x - v.y, tsum, p3[u], 0, 0, 0);
+      }
+    }
+  };
+  const int nks = (C + 3) >> 2;  // (<= 32)
+  cplx t0 = ldt(0), t1 = ldt(1);
+  for (int s = 0; s < nks; s += 2) {
+    const cplx n0 = ldt(s + 2), n1 = ldt(s + 3);  // (zero past C)
+    kstep(s, t0);
+    if (s + 1 < nks) kstep(s + 1, t1);
+    t0 = n0;
+    t1 = n1;
+  }
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const double re = TR ? p1[u][q] - p2[u][q] : p1[u][q] + p2[u][q];
+      const double im = TR ? p3[u][q] - p1[u][q] - p2[u][q] : p3[u][q] - p1[u][q] + p2[u][q];
+      // accumulator element (row lk + 4 q, column li) of the tile
+      const int kq = 16 * (ct + u) + (TR ? li : lk + 4 * q);
+      const int o = 16 * rt + (TR ? lk + 4 * q : li);  // the theta-side index
+      if (kq < k && o < outer) {
+        const int ch = TR ? chl : chr;
+        const int s = o >= ch, b = o - s * ch;
+        const double f1 = rcp[kVlRcpSig + kq], f2 = rcp[(TR ? kVlRcpLl : kVlRcpLr) + b];
+        const cplx g = aqc::cmk(re * f1 * f2, im * f1 * f2);
+        if (TR) aqc::stg(j.gp + s * half + (size_t)b * cap + kq, g);  // Gp'[s1][l][kq]
+        else aqc::stg(j.gq + s * half + (size_t)kq * cap + b, g);     // Gq'[s2][kq][r]
+      }
+    }
+  }
+}
+__device__ __forceinline__ void split_lds_chain(const TwoSiteJob& j, int tid) {
+  const bool tr = 2 * j.dims[0] >= 2 * j.dims[2];  // (qr = 1)
+  if (tr) split_lds_body<true>(j, tid);
+  else split_lds_body<false>(j, tid);
+}
+// done: what the Gram body's epilogue has already done (chain_jacobi)
+__device__ __forceinline__ void chain_split(const TwoSiteJob& j, int done) {
   const int tid = fresh_tid();
-  if (!copied) split_copy_body(j, tid, 1024);
+  if (done == 3) {
+    split_lds_chain(j, tid);
+    return;
+  }
+  if (done != 2) split_copy_body(j, tid, 1024);
   split_gemm_chain(j, tid);
 }
 
@@ -1366,7 +1483,7 @@ __global__ __launch_bounds__(1024) void k_chain(const ChainJob* __restrict__ cha
     if (done == 0) chain_rank(j);
     __syncthreads();
     tick(2);
-    chain_split(j, done == 2);
+    chain_split(j, done);
     __syncthreads();
     tick(3);
   }
@@ -2110,10 +2227,12 @@ int aqc_mps_chain_ticks(double* out) {
 }
 
 int aqc_mps_set_chain_epilogue(int mode) {
-  AQC_REQUIRE(mode >= 0 && mode <= 2, "aqc_mps_set_chain_epilogue: 0, 1 or 2");
+  AQC_REQUIRE(mode >= 0 && mode <= 3, "aqc_mps_set_chain_epilogue: 0, 1, 2 or 3");
   g_chain_epilogue = mode;
   return AQC_OK;
 }
+
+int aqc_mps_get_chain_epilogue(void) { return g_chain_epilogue; }
 
 int aqc_mps_chain_epilogue_stats(double* out) {
   AQC_REQUIRE(out, "aqc_mps_chain_epilogue_stats: null argument");

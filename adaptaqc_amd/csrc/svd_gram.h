@@ -381,12 +381,52 @@ __device__ __forceinline__ double rayleigh(int i, int C, const double* zb, const
   return s2 > 0.0 ? s2 : 0.0;
 }
 
+// Chain epilogue 3: S6 leaves V (128 x 64, zero past C rows and K columns) in the dynamic LDS for the
+// chain's split (split_lds_chain, mps.hip) instead of W = V Sigma in the work buffer.  Element (row,
+// col) sits at kVlPos: the column index swizzled by row & 15, so that 16 lanes along a row (the split's
+// MFMA operand, S6's accumulator layout) and 16 lanes along a column (the copied site's Gamma, lanes
+// along its fastest index) both touch every LDS bank once.  After V, three vectors of 64 reciprocals
+// with zeros past their ends and where the value is zero (the d != 0 guard of split_copy_body):
+// 1 / sigma_k, 1 / ll[l], 1 / lr[r].
+constexpr int kVlElems = 128 * 64;  // complex
+constexpr int kVlRcpSig = 0, kVlRcpLl = 64, kVlRcpLr = 128, kVlRcpLen = 192;  // doubles after V
+static_assert(kChainLdsBytes >= kVlElems * 16 + kVlRcpLen * 8, "V and the reciprocals exceed the chain's LDS");
+__device__ __forceinline__ int kVlPos(int row, int col) { return row * 64 + (col ^ (row & 15)); }
+
+// The tail of s6_back on chain epilogue 3's route, after the last reflector block's barrier, when every
+// LDS region of the loop is dead: V as it stands in the accumulators (zero past row C and column K,
+// so the whole 128 x 64 is written), and the reciprocals; the chain's barrier after the SVD phase
+// orders both before the split's reads.  (A call: it stays out of the body's register allocation.)
+__device__ __noinline__ void s6_leave_lds(const TwoSiteJob& j, aqc::d4_t vre0, aqc::d4_t vre1, aqc::d4_t vim0,
+                                          aqc::d4_t vim1, int K, const double* s_sig2) {
+  extern __shared__ double2 xbuf[];
+  cplx* Vl = xbuf;
+  double* rcp = reinterpret_cast<double*>(xbuf + kVlElems);
+  const int tid = fresh_tid(), lane = tid & 63, wave = tid >> 6;
+  const int nt = wave & 3, mg = wave >> 2, li = lane & 15, lk = lane >> 4;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    Vl[kVlPos(32 * mg + lk + 4 * q, 16 * nt + li)] = aqc::cmk(vre0[q], vim0[q]);
+    Vl[kVlPos(32 * mg + 16 + lk + 4 * q, 16 * nt + li)] = aqc::cmk(vre1[q], vim1[q]);
+  }
+  if (tid < kVlRcpLen) {
+    const int o = tid & 63;
+    double x;
+    if (tid < kVlRcpLl) x = o < K ? sqrt(s_sig2[o]) : 0.0;
+    else if (tid < kVlRcpLr) x = o < j.dims[0] ? aqc::ldg(j.ll + o) : 0.0;
+    else x = o < j.dims[2] ? aqc::ldg(j.lr + o) : 0.0;
+    rcp[tid] = x != 0.0 ? 1.0 / x : 0.0;
+  }
+}
+
 // S6's block loop: V (C x 64 from column c0 of Z, in the MFMA accumulator layout -- see
 // gram_svd_body) -= Y (T (Y^H V)) over the reflector blocks from the last, then W columns c0 + col
-// = V sigma into the work buffer.  Every thread of the workgroup.
+// = V sigma into the work buffer (lds, and the rank rule kept *s_fk > 0 columns: V into the LDS
+// instead, see kVlPos).  Every thread of the workgroup.
 __device__ __forceinline__ void s6_back(const TwoSiteJob& j, cplx* hh, int C, int K, int c0, aqc::d4_t (&vre)[2],
                                         aqc::d4_t (&vim)[2], const double* s_sig2, int tid, int lane, int wave,
-                                        int wave_s, bool copy = false, bool gtr = false, const int* s_fk = nullptr) {
+                                        int wave_s, bool copy = false, bool gtr = false, const int* s_fk = nullptr,
+                                        bool lds = false) {
   extern __shared__ double2 xbuf[];
   const int nt = wave & 3, mg = wave >> 2, li = lane & 15, lk = lane >> 4;
   // LDS (complex units): Y [128][16] (column index swizzled by row & 15: conflict-free reads along
@@ -507,6 +547,10 @@ __device__ __forceinline__ void s6_back(const TwoSiteJob& j, cplx* hh, int C, in
       }
     }
     __syncthreads();  // B5: Y, W2 and the partials are overwritten next block
+  }
+  if (lds && *s_fk > 0) {  // (uniform; *s_fk: written before this call's first barrier)
+    s6_leave_lds(j, vre[0], vre[1], vim[0], vim[1], K, s_sig2);
+    return;
   }
   {  // the reflectors are dead (last read before B1 of the last block): W overwrites them (a
      // first pass of K > 64 writes columns 64.. past them)
@@ -1570,13 +1614,13 @@ int gram_svd_body(const TwoSiteJob& j, int epi) {
       vim[t][q] = 0.0;
     }
   }
-  // ---- the fused chain's epilogue (epi: 1 the rank, 2 also the copied site; 0 from the lock-step
-  // kernel), for an update that will return 1: sigma is final here and comes out of S4 / S5 in
+  // ---- the fused chain's epilogue (epi: 1 the rank, 2 also the copied site, 3 the rank and V left in
+  // the LDS for the chain's split; 0 from the lock-step kernel), for an update that will return 1: sigma is final here and comes out of S4 / S5 in
   // descending order, so rank_body's sort is the identity unless two Rayleigh quotients of a
   // cluster came out swapped.  Wave 0 checks that under rank_body's order (ties by index, so >=),
   // thread 0 runs rank_rule on sigma in the LDS (s_err is dead since gram_keep) and the wave writes
   // what rank_body writes; an unsorted sigma leaves the update to rank_body (s_fk = 0). ----
-  if (epi == 2 && j.qr == 0) epi = 1;  // (the copy below writes the qr = 1 side, the chain's)
+  if (epi >= 2 && j.qr == 0) epi = 1;  // (the copy below, and 3's split, serve the qr = 1 side, the chain's)
   if (epi && !s_cert && wave == 0) {  // (uniform per wave)
     const double sg = lane < K ? sqrt(s_sig2[lane]) : 0.0;
     s_err[lane] = sg;
@@ -1600,7 +1644,8 @@ int gram_svd_body(const TwoSiteJob& j, int epi) {
       aqc::stg(j.sig + lane + kSigMax, sg);
     }
   }
-  s6_back(j, hh, C, K, 0, vre, vim, s_sig2, tid, lane, wave, wave_s, epi == 2 && !s_cert, tr, &s_fk);
+  s6_back(j, hh, C, K, 0, vre, vim, s_sig2, tid, lane, wave, wave_s, epi == 2 && !s_cert, tr, &s_fk,
+          epi == 3 && !s_cert);
   tick(4);
   }  // (K <= 64)
   const int fk = (epi && !s_cert && K <= kGramNarrowK) ? __builtin_amdgcn_readfirstlane(s_fk) : 0;  // (uniform)
@@ -1613,7 +1658,8 @@ int gram_svd_body(const TwoSiteJob& j, int epi) {
     atomicMax(&j.flags[2], 1);
     atomicAdd(&g_gram_stats[1], 1ull);
   }
-  return fk ? 2 + epi : 1;  // 3: the rank is decided, 4: and the copied site written
+  // 3: the rank is decided, 4: and the copied site written, 5: the rank is decided and V is in the LDS
+  return fk ? 2 + epi : 1;
 }
 
 // After gram_svd_body returned 2 (its kept count assumed the values in CHOP's error band chopped):

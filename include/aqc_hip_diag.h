@@ -107,11 +107,18 @@ int aqc_scratch_stats(double* out);
 int aqc_mps_set_fused_chain(int on);
 /* What the fused chain's Gram SVD does itself for an update it takes on its narrow path (K <= 64, no
    certificate), after checking that sigma left it sorted: mode 0 nothing (the chain's rank and copy
-   phases run), 1, the default, the rank decision (reduce_zeros, lambda, dims, the sorted sigma), 2
+   phases run), 1 the rank decision (reduce_zeros, lambda, dims, the sorted sigma), 2
    also the copied site's Gamma, written from the registers that hold V (AQC_CHAIN_EPILOGUE sets the
    initial value).  Every other update keeps
-   the chain's own phases; the results are bit for bit those of mode 0. */
+   the chain's own phases; the results of modes 1 and 2 are bit for bit those of mode 0.
+   Mode 3, the default: the rank decision as in 1, and the SVD leaves V and the reciprocals of sigma and of the
+   outer lambdas in the LDS instead of W = V Sigma in global memory; a split of its own writes the
+   copied site from there and runs the other site's GEMM on all 16 waves over the whole contraction
+   (three real products per complex one).  Its results equal mode 0's up to the rounding order of
+   that GEMM and of the scalings; updates it does not fuse are bit for bit mode 0's. */
 int aqc_mps_set_chain_epilogue(int mode);
+/* The current mode. */
+int aqc_mps_get_chain_epilogue(void);
 /* Updates since the last call (then reset): out[0] whose rank the Gram SVD decided itself, out[1]
    handed back to the chain's rank phase because sigma was not sorted; out[2]. */
 int aqc_mps_chain_epilogue_stats(double* out);
