@@ -97,21 +97,29 @@ class SamplingSimulator:
     MAX_NOISY_QUBITS, run it as MPS trajectories (aqc_mps_traj_sample) under the simulator's
     truncation options.  Opt-in, because an MPS trajectory costs about three two-site SVDs per noisy
     gate: every Kraus operator has to meet the orthogonality centre.  The same flag and the same rule
-    (``_trajectory_engine``) put QiskitSamplingBackend's noisy pair tomography on the MPS engine."""
+    (``_trajectory_engine``) put QiskitSamplingBackend's noisy pair tomography on the MPS engine.
+
+    ``mps_pauli_readout`` (needs ``mps_trajectories``): the same rule puts the noisy Pauli readout of
+    ``pauli_counts`` on the MPS engine (aqc_mps_traj_pauli_counts: every term read from each trajectory
+    by a transfer chain over its support); without it ``pauli_counts`` refuses a noise model there.
+    Opt-in like the other two."""
 
     name = "hip_sampling_simulator"
     METHODS = ("automatic", "statevector", "matrix_product_state")
     MAX_NOISY_QUBITS = 24  # aqc_sv_traj_sample's limit
 
     def __init__(self, method="automatic", seed=None, mps_truncation_threshold=1e-16, max_chi=None,
-                 mps_trajectories=False):
+                 mps_trajectories=False, mps_pauli_readout=False):
         if method not in self.METHODS:
             raise ValueError(f"method must be one of {self.METHODS}")
+        if mps_pauli_readout and not mps_trajectories:
+            raise ValueError("mps_pauli_readout=True needs mps_trajectories=True")
         self.options = SimpleNamespace(method=method, matrix_product_state_truncation_threshold=mps_truncation_threshold,
                                        matrix_product_state_max_bond_dimension=max_chi)
         self.seed = int(seed) if seed is not None else int(np.random.SeedSequence().generate_state(2, np.uint32).view(np.uint64)[0])
         self.runs = 0
         self.mps_trajectories = bool(mps_trajectories)
+        self.mps_pauli_readout = bool(mps_pauli_readout)
         self._last = None  # (n, method, ops bytes, device state)
 
     def __getstate__(self):
@@ -242,9 +250,9 @@ class SamplingSimulator:
         return SamplingJob(SamplingResult(counts))
 
     def _noisy_pauli_program(self, circuit, noise_model):
-        """(rows, n_events, effects) of the noisy Pauli readout on the statevector trajectory engine, or
-        None when ``noise_model`` has no effective error on the circuit or on the readout (one
-        simulation and binomial draws then)."""
+        """(rows, n_events, effects, engine) of the noisy Pauli readout, or None when ``noise_model`` has
+        no effective error on the circuit or on the readout (one simulation and binomial draws then).
+        The engine follows ``_trajectory_engine``; the MPS one needs ``mps_pauli_readout``."""
         from ..noise import readout_effects, trajectory_program
 
         if noise_model is None:
@@ -255,13 +263,19 @@ class SamplingSimulator:
         if n_events == 0 and not readout:
             return None
         if self._trajectory_engine(n) == "matrix_product_state":
-            raise NotImplementedError("the Pauli readout of MPS trajectories is not built: pauli_terms='device' "
-                                      "under a noise model runs statevector trajectories (method 'statevector', or "
-                                      f"'automatic' up to {self.MAX_NOISY_QUBITS} qubits)")
+            if not getattr(self, "mps_pauli_readout", False):
+                raise NotImplementedError("the Pauli readout of MPS trajectories is not built into this simulator: "
+                                          "pauli_terms='device' under a noise model runs statevector trajectories "
+                                          "(method 'statevector', or 'automatic' up to "
+                                          f"{self.MAX_NOISY_QUBITS} qubits) unless the simulator is built with "
+                                          "mps_trajectories=True, mps_pauli_readout=True")
+            self._refuse_correlated_on_mps(rows)
+            return rows, n_events, readout_effects(n, noise_model), "matrix_product_state"
         if n > self.MAX_NOISY_QUBITS:
-            raise NotImplementedError(f"statevector trajectories stop at {self.MAX_NOISY_QUBITS} qubits, and the "
-                                      "Pauli readout of MPS trajectories is not built")
-        return rows, n_events, readout_effects(n, noise_model)
+            raise NotImplementedError(f"statevector trajectories stop at {self.MAX_NOISY_QUBITS} qubits: use method "
+                                      "'automatic' or 'matrix_product_state' with mps_trajectories=True, "
+                                      "mps_pauli_readout=True")
+        return rows, n_events, readout_effects(n, noise_model), "statevector"
 
     def pauli_counts(self, circuit, labels, shots=1024, seed_simulator=None, noise_model=None):
         """int64 [len(labels)]: for every Pauli label (qiskit order, none all-identity) the number of +1
@@ -272,11 +286,13 @@ class SamplingSimulator:
         its classical operations) run once and every one draws a +-1 outcome per term
         (aqc_sv_traj_pauli_counts), the errors on the appended ``sdg`` / ``h`` / ``measure`` folded into
         POVM effects (noise.readout_effects): each term's count has the law of its own noisy circuit;
-        different terms share trajectories and are correlated.  Statevector trajectories only.
+        different terms share trajectories and are correlated.  With ``mps_pauli_readout`` the MPS
+        engine takes them where ``_trajectory_engine`` says so (aqc_mps_traj_pauli_counts, at the learned
+        capacity: an overflow grows it and runs the same trajectories again).
         Otherwise the circuit is simulated once (the cached state of ``run``), every term is taken by
         ``pauli_expect`` and its count is one binomial draw on the device (aqc_multinomial_counts).
         Seed and run counter as ``run``: one call advances the counter once."""
-        from ..device import multinomial_counts, trajectory_pauli_counts
+        from ..device import mps_trajectory_pauli_counts, multinomial_counts, trajectory_pauli_counts
         from ..paulis import terms_to_codes
 
         n = circuit.num_qubits
@@ -294,8 +310,11 @@ class SamplingSimulator:
             seed, run = self.seed, self.runs
             self.runs += 1
         if noisy is not None:
-            rows, n_events, effects = noisy
-            return trajectory_pauli_counts(n, rows, n_events, codes, effects, shots, seed, run)
+            rows, n_events, effects, engine = noisy
+            if engine == "statevector":
+                return trajectory_pauli_counts(n, rows, n_events, codes, effects, shots, seed, run)
+            return self._at_learned_capacity(
+                n, lambda **cap: mps_trajectory_pauli_counts(n, rows, n_events, codes, effects, shots, seed, run, **cap))
         ev = dev.pauli_expect(np.concatenate([codes, np.zeros((1, n), dtype=np.uint8)]))
         v, w = ev[:-1], ev[-1]  # w = <psi|psi>: below 1 for a truncated MPS
         probs = np.stack([np.maximum(0.0, (w + v) / 2), np.maximum(0.0, (w - v) / 2)], axis=1)
@@ -411,7 +430,10 @@ class QiskitSamplingBackend(AQCBackend):
       from one ``SamplingSimulator.pauli_counts`` call -- under a noise model ``shots`` trajectories,
       each read out for every term (aqc_sv_traj_pauli_counts).  A term's estimate has the law of the
       reference's circuit for that term; different terms share trajectories and are correlated.
-      Statevector trajectories only: the Pauli readout of MPS trajectories is not built.
+      Statevector trajectories up to 24 qubits; with a simulator built with ``mps_trajectories=True,
+      mps_pauli_readout=True``, method "matrix_product_state", and "automatic" above 24 qubits, run MPS
+      trajectories instead (aqc_mps_traj_pauli_counts: every term read from each trajectory by a transfer
+      chain over its support, any number of general factors a term).
     """
 
     TOMOGRAPHY_MODES = (None, "circuits", "device")

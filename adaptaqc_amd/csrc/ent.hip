@@ -1117,6 +1117,12 @@ int aqc::mps_envs_batch(aqc_mps_s** hs, int ns, size_t extra_bytes, const char* 
   return AQC_OK;
 }
 
+// What mps_envs_batch lays out per state (see mps_internal.h).
+size_t aqc::env_state_bytes(int n, int cap) {
+  const size_t cc = (size_t)cap * cap;
+  return (2 * (size_t)(n + 1) * cc + 4 * cc) * sizeof(cplx);
+}
+
 // What aqc_mps_pair_rdms_batch lays out per state in the per-device buffer: both environment sides,
 // the chains' scratch, P and U of every site, the chains of the `na` distinct lower qubits and the
 // n x n table of 4x4 blocks (see mps_internal.h).

@@ -508,6 +508,9 @@ int mps_right_envs(aqc_mps_s* h, size_t extra_bytes, const cplx** renv, void** e
 // names the launches for aqc_timing_query; the rest as above (*extra is 16-byte aligned).
 int mps_envs_batch(aqc_mps_s** hs, int ns, size_t extra_bytes, const char* family, const cplx** lenv,
                    size_t* state_stride, void** extra, hipStream_t* stream);
+// Bytes of that buffer mps_envs_batch takes per state of n qubits at capacity cap (both sides and the
+// chains' scratch), for a caller that budgets device memory.
+size_t env_state_bytes(int n, int cap);
 // Bytes of that buffer aqc_mps_pair_rdms_batch takes per state of n qubits at capacity cap, for pairs
 // with `na` distinct lower qubits (a caller that budgets device memory sizes its batches by it).
 size_t pair_rdm_state_bytes(int n, int cap, int na);

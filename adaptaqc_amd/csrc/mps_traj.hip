@@ -35,11 +35,32 @@
 // k_mps_traj_pair_draw -- one thread per (state, pair) -- forms the four outcome probabilities from
 // the RDM and the two qubits' POVM effects with the arithmetic of k_sv_traj's pair ending
 // (pair_draw.h), draws one outcome and adds it to the integer count table on the device.
+//
+// The noisy Pauli readout (aqc_mps_traj_pauli_counts): the pair readout's schedule, nshots trajectories,
+// every trajectory serving every term.  A noisy readout turns a term's letter on qubit q into the
+// Hermitian 2x2 factor D_q = E+ - E- (an identity part beside the Pauli one), so the chain of pauli.hip
+// is restated for a general factor per site: with A_i^s = Gamma_i^s lambda_{i+1} and the identity
+// environments L_b, R_b of ent.hip's chains (no canonical form assumed), a term with support lo..hi is
+//   E = L_lo;  for i = lo..hi:  E'[b'][k'] = sum_{s,t} D_i[s][t] conj(A_s[b][b']) E[b][k] A_t[k][k'];
+//   v = Re sum E[b][k] R_{hi+1}[k][b].
+// k_mps_traj_pauli_chain gives each (term, state) item to one 256-thread workgroup that needs nothing
+// from any other (no counters, no hand-offs: nothing in it can wait) and walks the items wg, wg + grid,
+// ...; a site is two aqc::block_cgemm products on the FP64 matrix cores, T = E [A_0 | A_1] (chi_l x
+// 2 chi_r, contraction chi_l) and E' = sum_{(t,b)} (sum_s D[s][t] conj(A_s[b][b'])) T_t[b][k'] (chi_r x
+// chi_r, contraction 2 chi_l): 4 chi^3 complex multiply-adds (32 chi^3 flops); E and both slices of Gamma
+// read and T written by the first product, both slices per (t, b) and T read and E' written by the
+// second (12 chi^2 complex of traffic, 2 chi^2 more than a Pauli letter's one slice per t), whatever D
+// is -- a general factor costs the same at any number per term.  E and T
+// (3 cap^2 complex) are the workgroup's slice of a bounded workspace.  One more item per state, the
+// all-identity term on site 0, gives w = <psi|psi>.  k_mps_traj_pauli_draw -- one thread per (state,
+// term) -- draws the parity from (v, w) and adds to the 64-bit table on the device.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <numeric>
 #include <vector>
 
+#include "aqc_gemm.h"
 #include "mps_internal.h"
 #include "pair_draw.h"
 #include "sample_rng.h"
@@ -62,7 +83,12 @@ constexpr int kReadoutStates = 16;  // states per RDM sweep of the pair readout
 constexpr size_t kBatchBudgetBytes = (size_t)4 << 30;
 constexpr int kChunkRows = 64;  // schedule rows per run_waves call (bounds the job staging)
 int g_forced_batch = 0;
-int g_forced_readout = 0;  // aqc_mps_traj_set_readout_batch: states per RDM sweep of the pair readout
+int g_forced_readout = 0;  // aqc_mps_traj_set_readout_batch: states per sweep of the pair / Pauli readout
+constexpr int kMaxTerms = 65536;
+constexpr int kCT = 256;  // threads of k_mps_traj_pauli_chain
+constexpr size_t kChainWsBytes = (size_t)512 << 20;  // bound of the chain kernel's E / T workspace
+constexpr int kChainMaxWg = 2048;                    // and of its grid (8 workgroups a CU)
+constexpr int kPauliReadoutStates = 128;             // states per sweep of the Pauli readout
 
 __device__ __forceinline__ double wave_sum(double v) {
   for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d, 64);
@@ -205,6 +231,131 @@ __global__ __launch_bounds__(kDT) void k_mps_traj_pair_draw(const PairDrawJob j)
   const int k = aqc::pair_outcome(eh, el, d, ox, oy, uu);
   if (j.outcomes) j.outcomes[(size_t)local * j.npairs + pj] = (uint8_t)k;
   atomicAdd(j.counts + ((size_t)pj * 9 + s9) * 4 + k, 1ULL);
+}
+
+// ---- the Pauli readout -----------------------------------------------------------------------
+struct ChainState {
+  const cplx* gam;
+  const double* lam;
+  const int* dims;
+  const cplx* Lenv;  // L_b at b cap^2 [bra][ket], row stride cap (b = 0 .. n-1)
+  const cplx* Renv;  // R_b at b cap^2 [ket][bra], row stride cap (b = 1 .. n)
+};
+
+struct ChainJob {
+  const ChainState* states;  // the sweep's nr states
+  const uint8_t* codes;      // nterms x n
+  const int* terms;          // per issued term: lo, hi, index (index nterms: the all-identity term, w)
+  const double* dtab;        // [n][3][4]: (D00, D11, Re D01, Im D01) of qubit q under letter c at (3 q + c - 1) 4
+  int n, cap, nterms, nr;
+  cplx* ws;     // per workgroup 3 cap^2: E (cap x cap), T (cap x 2 cap)
+  double* out;  // [nr][nterms + 1], the last column w
+};
+
+// sum over the block in a fixed order (lane tree, then the four waves in index order); the result in thread 0
+__device__ __forceinline__ double chain_block_sum(double v, double* red) {
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = 0.0;
+  if (threadIdx.x == 0) s = ((red[0] + red[1]) + red[2]) + red[3];
+  __syncthreads();
+  return s;
+}
+
+__global__ __launch_bounds__(kCT) void k_mps_traj_pauli_chain(const ChainJob j) {
+  __shared__ aqc::GemmLds lds;
+  __shared__ double red[4];
+  const int n = j.n, cap = j.cap, nout = j.nterms + 1;
+  const size_t cc = (size_t)cap * cap;
+  cplx* E = j.ws + (size_t)blockIdx.x * 3 * cc;
+  cplx* T = E + cc;
+  const int items = nout * j.nr;
+  for (int item = blockIdx.x; item < items; item += gridDim.x) {
+    const int it = item / j.nr, st = item % j.nr;
+    const int lo = j.terms[3 * it], hi = j.terms[3 * it + 1], term = j.terms[3 * it + 2];
+    const ChainState& S = j.states[st];
+    const uint8_t* code = term < j.nterms ? j.codes + (size_t)term * n : nullptr;
+    const cplx* cur = S.Lenv + (size_t)lo * cc;
+    for (int i = lo; i <= hi; ++i) {
+      const int cl = min(S.dims[i], cap), cr = min(S.dims[i + 1], cap);
+      const cplx* g = S.gam + (size_t)i * 2 * cc;
+      const double* lam = S.lam + (size_t)(i + 1) * cap;
+      // T[b][t cap + k'] = sum_k E[b][k] A_t[k][k']
+      aqc::block_cgemm<true, false, true>(
+          cl, 2 * cr, cl, [&](int r, int k) { return cur[(size_t)r * cap + k]; },
+          [&](int k, int c) {
+            const int t = c >= cr ? 1 : 0, rr = c - t * cr;
+            return aqc::cscale(aqc::ldg(g + (size_t)t * cc + (size_t)k * cap + rr), aqc::ldg(lam + rr));
+          },
+          [&](int r, int c, cplx v) { T[(size_t)r * 2 * cap + (c >= cr ? cap + c - cr : c)] = v; }, lds);
+      __syncthreads();
+      // the site's factor: column t of D is (D00, conj(D01)) for t = 0 and (D01, D11) for t = 1
+      const int p = code ? code[i] : 0;
+      double d00 = 1.0, d11 = 1.0, dx = 0.0, dy = 0.0;
+      if (p) {
+        const double* d = j.dtab + (size_t)(3 * i + p - 1) * 4;
+        d00 = aqc::ldg(d), d11 = aqc::ldg(d + 1), dx = aqc::ldg(d + 2), dy = aqc::ldg(d + 3);
+      }
+      // E'[b'][k'] = sum_{(t, b)} (sum_s D[s][t] conj(A_s[b][b'])) T[b][t cap + k']
+      aqc::block_cgemm<false, false, true>(
+          cr, cr, 2 * cl,
+          [&](int r, int kk) {
+            const int t = kk >= cl ? 1 : 0, b = kk - t * cl;
+            const size_t o = (size_t)b * cap + r;
+            const cplx a0 = aqc::cconj(aqc::ldg(g + o)), a1 = aqc::cconj(aqc::ldg(g + cc + o));
+            const cplx c0 = t ? aqc::cmk(dx, dy) : aqc::cmk(d00, 0.0), c1 = t ? aqc::cmk(d11, 0.0) : aqc::cmk(dx, -dy);
+            return aqc::cscale(aqc::cfma(c1, a1, aqc::cmul(c0, a0)), aqc::ldg(lam + r));
+          },
+          [&](int kk, int c) {
+            const int t = kk >= cl ? 1 : 0, b = kk - t * cl;
+            return T[(size_t)b * 2 * cap + (size_t)t * cap + c];
+          },
+          [&](int r, int c, cplx v) { E[(size_t)r * cap + c] = v; }, lds);
+      __syncthreads();
+      cur = E;
+    }
+    const int d = min(S.dims[hi + 1], cap);
+    const cplx* R = S.Renv + (size_t)(hi + 1) * cc;
+    double acc = 0.0;
+    for (int e = threadIdx.x; e < d * d; e += kCT) {
+      const int b = e / d, k = e % d;
+      const cplx x = cur[(size_t)b * cap + k], y = aqc::ldg(R + (size_t)k * cap + b);
+      acc += fma(x.x, y.x, -x.y * y.y);
+    }
+    const double s = chain_block_sum(acc, red);  // (its barriers also fence E before the next item's stores)
+    if (threadIdx.x == 0) j.out[(size_t)st * nout + term] = s;
+  }
+}
+
+// The draw of the sweep's nr states: state s of the sweep is trajectory traj0 + s, state local0 + s of
+// the batch (the batch's uniforms and output rows are indexed by that).
+struct PauliDrawJob {
+  const double* vals;        // [nr][nterms + 1]: v of every term, then w
+  const double* u;           // null, or the batch's [state][nper]
+  unsigned long long* plus;  // [nterms]
+  double* values;            // null, or the batch's [state][nterms]
+  double* norms;             // null, or the batch's [state]
+  uint8_t* outcomes;         // null, or the batch's [state][nterms]
+  uint64_t seed, run;
+  int traj0, local0, nr, nterms, nev, nper;
+};
+
+// One thread per (state, term): no sum crosses a thread; the table takes integer atomics only.
+__global__ __launch_bounds__(kDT) void k_mps_traj_pauli_draw(const PauliDrawJob j) {
+  const int e = blockIdx.x * kDT + threadIdx.x;
+  if (e >= j.nr * j.nterms) return;
+  const int s = e / j.nterms, tj = e - s * j.nterms;
+  const int t = j.traj0 + s, local = j.local0 + s;
+  const double v = j.vals[(size_t)s * (j.nterms + 1) + tj], w = j.vals[(size_t)s * (j.nterms + 1) + j.nterms];
+  const double pp = fmax(0.0, 0.5 * (w + v)), pm = fmax(0.0, 0.5 * (w - v));
+  const double uu = j.u ? aqc::ldg(j.u + (size_t)local * j.nper + j.nev + tj)
+                        : aqc::sample_uniform(j.seed, j.run, (uint64_t)t, (uint32_t)(j.nev + tj));
+  const int o = uu * (pp + pm) >= pp ? 1 : 0;
+  if (j.values) j.values[(size_t)local * j.nterms + tj] = v;
+  if (j.norms && tj == 0) j.norms[local] = w;
+  if (j.outcomes) j.outcomes[(size_t)local * j.nterms + tj] = (uint8_t)o;
+  if (!o) atomicAdd(j.plus + tj, 1ULL);
 }
 
 // ---- the site-level schedule -----------------------------------------------------------------
@@ -653,6 +804,199 @@ int aqc_mps_traj_pair_tomo(int n, int chi_cap, double threshold, int max_chi, co
   }
   // the table accumulated on the device across the batches
   AQC_HIP_CHECK(hipMemcpyAsync(counts, dj.counts, (size_t)npairs * 36 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  AQC_HIP_CHECK(hipStreamSynchronize(st));
+  return AQC_OK;
+}
+
+int aqc_mps_traj_pauli_counts(int n, int chi_cap, double threshold, int max_chi, const aqc_op_t* prog, int nprog,
+                              const uint8_t* codes, int nterms, const double* effects, int nshots, uint64_t seed,
+                              uint64_t run, const double* u, int64_t* plus, double* values, double* norms,
+                              uint8_t* outcomes) {
+  t_entry = "aqc_mps_traj_pauli_counts";
+  AQC_REQUIRE(plus && codes && effects && nprog >= 0 && (prog || nprog == 0), "aqc_mps_traj_pauli_counts: null argument");
+  AQC_REQUIRE(n >= 1 && n <= 4096, "aqc_mps_traj_pauli_counts: n must be in 1 .. 4096");
+  AQC_REQUIRE(chi_cap >= 1 && chi_cap <= aqc::kMaxCap, "aqc_mps_traj_pauli_counts: chi_cap must be in [1, 1024]");
+  AQC_REQUIRE(nterms >= 1 && nterms <= kMaxTerms, "aqc_mps_traj_pauli_counts: nterms must be in 1 .. 65536");
+  AQC_REQUIRE(nshots >= 1 && nshots <= kMaxShots, "aqc_mps_traj_pauli_counts: nshots must be in 1 .. 2^30");
+  if (int rc = aqc::check_effects(n, effects, t_entry)) return rc;
+  // supports, issued by decreasing length so that the long chains start first; last the all-identity
+  // term on site 0 (L_0, one identity step, R_1): w
+  const int nout = nterms + 1;
+  std::vector<int> terms(3 * (size_t)nout);
+  double steps = 1.0;
+  {
+    std::vector<int> lo(nterms), hi(nterms), order(nterms);
+    for (int t = 0; t < nterms; ++t) {
+      int a = -1, b = -1;
+      for (int q = 0; q < n; ++q) {
+        const uint8_t c = codes[(size_t)t * n + q];
+        if (c > 3) return fail("a Pauli code must be 0 (I), 1 (X), 2 (Y) or 3 (Z)");
+        if (c) {
+          if (a < 0) a = q;
+          b = q;
+        }
+      }
+      if (a < 0) return fail("an all-identity term (its value is 1: the caller answers it)");
+      lo[t] = a;
+      hi[t] = b;
+      steps += (double)(b - a + 1);
+    }
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return hi[a] - lo[a] > hi[b] - lo[b]; });
+    for (int k = 0; k < nterms; ++k) {
+      terms[3 * k] = lo[order[k]];
+      terms[3 * k + 1] = hi[order[k]];
+      terms[3 * k + 2] = order[k];
+    }
+    terms[3 * nterms] = terms[3 * nterms + 1] = 0;
+    terms[3 * nterms + 2] = nterms;
+  }
+  // D = E+ - E- of every (qubit, letter)
+  std::vector<double> dtab((size_t)n * 12);
+  for (size_t qb = 0; qb < (size_t)n * 3; ++qb)
+    for (int e = 0; e < 4; ++e) dtab[qb * 4 + e] = effects[qb * 8 + e] - effects[qb * 8 + 4 + e];
+  TrajSched sch;
+  if (int rc = build_schedule(n, prog, nprog, sch, false)) return rc;
+  const int nev = sch.nev, nper = nev + nterms;
+  if (u)
+    for (size_t e = 0, nu = (size_t)nshots * nper; e < nu; ++e)
+      if (!(u[e] >= 0.0 && u[e] < 1.0)) return fail("u must lie in [0, 1)");
+  // The batch: B trajectories run the schedule together and are read out R at a time, within the
+  // budget less the chains' workspace.  The environments are two dependent n-step chains per state and
+  // the Pauli chains one workgroup per (term, state), so a sweep wants many states: R up to 128 (of 16 /
+  // 32 / 64 / 128 the fastest on 50 qubits and 297 terms, profiles/mps_trajectory_pauli.json), at most
+  // half of what is left, and B takes the rest.
+  const size_t cc = (size_t)chi_cap * chi_cap;
+  const size_t per_wg = 3 * cc * sizeof(cplx);
+  const size_t max_wg = std::max<size_t>(1, std::min<size_t>((size_t)kChainMaxWg, kChainWsBytes / per_wg));
+  const size_t budget = kBatchBudgetBytes - max_wg * per_wg;
+  const size_t evolve = evolve_state_bytes(sch, n, chi_cap);
+  const size_t readout = aqc::env_state_bytes(n, chi_cap) + (size_t)nout * sizeof(double);
+  int R = (int)std::max<size_t>(1, std::min<size_t>({(size_t)kPauliReadoutStates, (size_t)nshots, budget / 2 / readout}));
+  const size_t left = budget - std::min(budget, (size_t)R * readout);
+  int B = (int)std::min<size_t>({(size_t)nshots, (size_t)kMaxBatch, std::max<size_t>(1, left / evolve)});
+  if (g_forced_batch > 0) {  // what a forced batch leaves of the budget
+    B = std::min(nshots, g_forced_batch);
+    const size_t held = std::min(budget, (size_t)B * evolve);
+    R = (int)std::max<size_t>(1, std::min<size_t>((size_t)R, (budget - held) / readout));
+  }
+  R = std::min(R, B);
+  if (g_forced_readout > 0) R = std::min(B, g_forced_readout);
+  const int nwg = (int)std::min<size_t>(max_wg, (size_t)R * nout);
+  Handles hs;
+  if (int rc = hs.create(B, n, chi_cap, threshold, max_chi)) return rc;
+  hipStream_t st = aqc::mps_stream();
+  const size_t ub = u ? up256((size_t)B * nper * sizeof(double)) : 0;
+  const size_t cb = up256((size_t)nterms * n);
+  const size_t tb = up256(terms.size() * sizeof(int));
+  const size_t db = up256(dtab.size() * sizeof(double));
+  const size_t pb = up256((size_t)nterms * sizeof(int64_t));
+  const size_t vb = values ? up256((size_t)B * nterms * sizeof(double)) : 0;
+  const size_t nb8 = norms ? up256((size_t)B * sizeof(double)) : 0;
+  const size_t ob = outcomes ? up256((size_t)B * nterms) : 0;
+  const size_t sb = up256((size_t)R * sizeof(ChainState));
+  const size_t rb = up256((size_t)R * nout * sizeof(double));
+  AQC_HIP_CHECK(hipStreamSynchronize(st));  // (the scratch may be regrown)
+  aqc::DevScratch& scr = g_scr.here();
+  if (int rc = scr.ensure(ub + cb + tb + db + pb + vb + nb8 + ob + sb + rb + (size_t)nwg * per_wg)) return rc;
+  char* at = scr.dev;
+  auto take = [&](size_t bytes) {
+    char* p = at;
+    at += bytes;
+    return p;
+  };
+  TrajCtx ctx;
+  std::memset(&ctx, 0, sizeof(ctx));
+  ctx.seed = seed;
+  ctx.run = run;
+  ctx.u = u ? (const double*)take(ub) : nullptr;
+  ctx.nev = nev;
+  ctx.nper = nper;
+  ChainJob cj;
+  std::memset(&cj, 0, sizeof(cj));
+  cj.codes = (const uint8_t*)take(cb);
+  cj.terms = (const int*)take(tb);
+  cj.dtab = (const double*)take(db);
+  cj.n = n;
+  cj.cap = chi_cap;
+  cj.nterms = nterms;
+  PauliDrawJob dj;
+  std::memset(&dj, 0, sizeof(dj));
+  dj.u = ctx.u;
+  dj.plus = (unsigned long long*)take(pb);
+  dj.values = values ? (double*)take(vb) : nullptr;
+  dj.norms = norms ? (double*)take(nb8) : nullptr;
+  dj.outcomes = outcomes ? (uint8_t*)take(ob) : nullptr;
+  dj.seed = seed;
+  dj.run = run;
+  dj.nterms = nterms;
+  dj.nev = nev;
+  dj.nper = nper;
+  cj.states = (const ChainState*)take(sb);
+  cj.out = (double*)take(rb);
+  cj.ws = (cplx*)take((size_t)nwg * per_wg);
+  dj.vals = cj.out;
+  AQC_HIP_CHECK(hipMemcpyAsync((void*)cj.codes, codes, (size_t)nterms * n, hipMemcpyHostToDevice, st));
+  AQC_HIP_CHECK(hipMemcpyAsync((void*)cj.terms, terms.data(), terms.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  AQC_HIP_CHECK(hipMemcpyAsync((void*)cj.dtab, dtab.data(), dtab.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  AQC_HIP_CHECK(hipMemsetAsync(dj.plus, 0, (size_t)nterms * sizeof(int64_t), st));
+  std::vector<std::vector<DevOp>> lists;
+  std::vector<ChainState> states(R);
+  for (int t0 = 0; t0 < nshots; t0 += B) {
+    const int nb = std::min(B, nshots - t0);
+    ctx.shot0 = t0;
+    if (t0 > 0)
+      for (int s = 0; s < nb; ++s)
+        if (int rc = aqc::mps_reset_zero(hs.h[s])) return rc;
+    if (u)
+      AQC_HIP_CHECK(hipMemcpyAsync((void*)ctx.u, u + (size_t)t0 * nper, (size_t)nb * nper * sizeof(double),
+                                   hipMemcpyHostToDevice, st));
+    if (int rc = run_rows(sch, hs.h.data(), nb, ctx, lists)) return rc;
+    for (int r0 = 0; r0 < nb; r0 += R) {
+      const int nr = std::min(R, nb - r0);
+      // both identity environments of the sweep's states (a Kraus row has broken Vidal form); the call
+      // returns with the stream idle, so the host copy of the states is free to be rewritten
+      const cplx* lenv = nullptr;
+      size_t stride = 0;
+      void* extra = nullptr;
+      hipStream_t est = nullptr;
+      if (int rc = aqc::mps_envs_batch(hs.h.data() + r0, nr, 0, "traj_pauli_env", &lenv, &stride, &extra, &est)) return rc;
+      for (int s = 0; s < nr; ++s) {
+        const aqc_mps_t h = hs.h[r0 + s];
+        states[s].gam = h->d.gam;
+        states[s].lam = h->d.lam;
+        states[s].dims = h->d.dims;
+        states[s].Lenv = lenv + (size_t)s * stride;
+        states[s].Renv = states[s].Lenv + (size_t)(n + 1) * cc;
+      }
+      AQC_HIP_CHECK(hipMemcpyAsync((void*)cj.states, states.data(), (size_t)nr * sizeof(ChainState), hipMemcpyHostToDevice, st));
+      cj.nr = nr;
+      const size_t items = (size_t)nr * nout;
+      // a site of a chain at capacity: 12 chi^2 complex moved, 4 chi^3 complex multiply-adds
+      aqc::KernelTimer::begin(st, "mps_traj_pauli_chain", (double)nr * steps * 12.0 * 16.0 * (double)cc,
+                              (double)nr * steps * 4.0 * 8.0 * (double)cc * chi_cap);
+      hipLaunchKernelGGL(k_mps_traj_pauli_chain, dim3((unsigned)std::min<size_t>((size_t)nwg, items)), dim3(kCT), 0, st, cj);
+      aqc::KernelTimer::end(st);
+      AQC_CHECK_LAUNCH();
+      dj.traj0 = t0 + r0;
+      dj.local0 = r0;
+      dj.nr = nr;
+      // each thread: v, w and u read, a value, a byte and a count written
+      aqc::KernelTimer::begin(st, "mps_traj_pauli_draw", (double)nr * nterms * (24.0 + 9.0 + 8.0), 0.0);
+      hipLaunchKernelGGL(k_mps_traj_pauli_draw, dim3((nr * nterms + kDT - 1) / kDT), dim3(kDT), 0, st, dj);
+      aqc::KernelTimer::end(st);
+      AQC_CHECK_LAUNCH();
+    }
+    if (values)
+      AQC_HIP_CHECK(hipMemcpyAsync(values + (size_t)t0 * nterms, dj.values, (size_t)nb * nterms * sizeof(double),
+                                   hipMemcpyDeviceToHost, st));
+    if (norms) AQC_HIP_CHECK(hipMemcpyAsync(norms + t0, dj.norms, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (outcomes)
+      AQC_HIP_CHECK(hipMemcpyAsync(outcomes + (size_t)t0 * nterms, dj.outcomes, (size_t)nb * nterms, hipMemcpyDeviceToHost, st));
+    AQC_HIP_CHECK(hipStreamSynchronize(st));  // the next batch overwrites the uniforms and the output rows
+  }
+  // the table accumulated on the device across the batches
+  AQC_HIP_CHECK(hipMemcpyAsync(plus, dj.plus, (size_t)nterms * sizeof(int64_t), hipMemcpyDeviceToHost, st));
   AQC_HIP_CHECK(hipStreamSynchronize(st));
   return AQC_OK;
 }

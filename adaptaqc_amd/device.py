@@ -428,6 +428,47 @@ def mps_trajectory_pair_tomography(n, rows, n_events, pairs, effects, shots, see
     return (counts, outcomes) if return_outcomes else counts
 
 
+def mps_trajectory_pauli_counts(n, rows, n_events, terms, effects, shots, seed, run=0, u=None, return_values=False,
+                                return_norms=False, return_outcomes=False, chi_cap=64, threshold=1e-16, max_chi=None):
+    """``trajectory_pauli_counts`` on the MPS engine (aqc_mps_traj_pauli_counts): the same arguments and
+    the same int64 [nterms] count of +1 parities, with no limit on the general factors of a term.  Every
+    one of the ``shots`` trajectories is an MPS of capacity ``chi_cap`` truncated by (``threshold``,
+    ``max_chi``), run through ``mps_trajectory_pair_tomography``'s schedule and read out for every term
+    by a transfer chain over the term's support; one that outgrows the capacity raises the capacity
+    AqcError.  With ``return_values`` also the float64 [shots, nterms] v = Re <psi_t|M_j|psi_t>, with
+    ``return_norms`` the float64 [shots] w = <psi_t|psi_t> (below 1 for a truncated trajectory; the draw
+    uses p+- = (w +- v) / 2, so nothing is renormalised), with ``return_outcomes`` the uint8
+    [shots, nterms] outcomes (1 = parity -1); the result is then the tuple
+    (plus[, values][, norms][, outcomes])."""
+    from . import paulis
+
+    n, shots, n_events = int(n), int(shots), int(n_events)
+    rows = np.ascontiguousarray(rows, dtype=_lib.OP_DTYPE)
+    _refuse_correlated_rows(rows, "mps_trajectory_pauli_counts")
+    if int(np.count_nonzero(rows["flags"] == _lib.OP_KRAUS1)) != n_events:
+        raise ValueError("mps_trajectory_pauli_counts: n_events does not match the program's Kraus rows")
+    codes = paulis.terms_to_codes(terms, n)
+    nterms = len(codes)
+    eff = np.ascontiguousarray(effects, dtype=np.float64)
+    if eff.shape != (n, 3, 2, 4):
+        raise ValueError(f"mps_trajectory_pauli_counts: effects must have shape {(n, 3, 2, 4)}")
+    up = _uniforms_arg(u, (shots, n_events + nterms))
+    plus = np.zeros(nterms, dtype=np.int64)
+    values = np.zeros((max(shots, 0), nterms)) if return_values else None
+    norms = np.zeros(max(shots, 0)) if return_norms else None
+    outcomes = np.zeros((max(shots, 0), nterms), dtype=np.uint8) if return_outcomes else None
+    _lib.check(_lib.lib().aqc_mps_traj_pauli_counts(n, int(chi_cap), float(threshold), int(max_chi or 0),
+                                                    _lib.ptr(rows) if len(rows) else None, len(rows),
+                                                    _lib.ptr(codes) if nterms else None, nterms, _lib.ptr(eff), shots,
+                                                    _u64(seed), _u64(run), _lib.ptr(up), _lib.ptr(plus),
+                                                    _lib.ptr(values) if return_values and nterms else None,
+                                                    _lib.ptr(norms) if return_norms and shots > 0 else None,
+                                                    _lib.ptr(outcomes) if return_outcomes and nterms else None))
+    out = ((plus,) + ((values,) if return_values else ()) + ((norms,) if return_norms else ())
+           + ((outcomes,) if return_outcomes else ()))
+    return out if len(out) > 1 else plus
+
+
 MPS_TRAJECTORY_COUNTS = ("gate_updates", "swap_updates", "centre_moves", "one_site_rows", "kraus_rows",
                          "measure_rows", "rows")
 

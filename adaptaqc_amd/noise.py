@@ -4,7 +4,8 @@ two-qubit Kraus sets (``QuantumError.two_qubit``, ``depolarizing_error(p, 2)``, 
 csrc/mps_traj.hip, aqc_mps_traj_sample, on an MPS), and the POVM effects of a noisy Pauli-basis
 readout for noisy pair tomography (``readout_effects``, aqc_sv_traj_pair_tomo / aqc_mps_traj_pair_tomo)
 and for the noisy Pauli readout of every term of an operator from each trajectory
-(aqc_sv_traj_pauli_counts, ``SamplingSimulator.pauli_counts``; statevector trajectories only).
+(aqc_sv_traj_pauli_counts on statevector trajectories, aqc_mps_traj_pauli_counts on MPS trajectories;
+``SamplingSimulator.pauli_counts``, the MPS engine with ``mps_pauli_readout=True``).
 
 Stands in for the parts of ``qiskit_aer.noise`` that the reference uses
 (``execute_kwargs={'noise_model': NoiseModel, 'shots': ...}``, approximate_compiler.py:93;
@@ -18,8 +19,7 @@ probability |K_k psi|^2 and applied to both qubits (matrix index 2 b(second list
 listed qubit), a two-qubit gate row's and Aer's convention).  It runs on the statevector trajectory
 engine (up to 24 qubits); the MPS trajectory engine refuses it by name.
 
-Out of scope: correlated errors on the MPS engine, the Pauli readout of MPS trajectories (not built:
-``pauli_counts`` raises for that engine), two errors on one instruction, readout-error
+Out of scope: correlated errors on the MPS engine, two errors on one instruction, readout-error
 matrices, reset, errors on gates of three or more qubits.
 """
 import numpy as np

@@ -291,7 +291,9 @@ def expectation_values_of_pauli_terms(circuit, labels, backend, backend_options=
       (``shots``, ``seed_simulator``), then the parity average.  A backend built with
       ``pauli_terms="device"`` hands all non-identity terms to one
       ``backend.simulator.pauli_counts`` call instead (under a noise model: ``shots`` trajectories,
-      each read out for every term); a term's value is (2 plus - shots) / shots.
+      each read out for every term -- statevector trajectories, or MPS trajectories on a simulator built
+      with ``mps_trajectories=True, mps_pauli_readout=True``); a term's value is
+      (2 plus - shots) / shots.
 
     ``circuit`` is not modified (its own measure instructions are ignored); ``backend_options`` are
     Aer's and have no meaning here."""

@@ -284,8 +284,8 @@ int aqc_mps_traj_sample(int n, int chi_cap, double threshold, int max_chi, const
    rows, Kraus rows, measurement rows, all rows. */
 #define AQC_OP_MEASURE1 2
 int aqc_mps_traj_plan(int n, const aqc_op_t* prog, int nprog, int* counts, aqc_op_t* sched, int sched_cap);
-/* Debugging: forces the batch size B of aqc_mps_traj_sample and aqc_mps_traj_pair_tomo (1 .. 4096; 0
-   restores the default). */
+/* Debugging: forces the batch size B of aqc_mps_traj_sample, aqc_mps_traj_pair_tomo and
+   aqc_mps_traj_pauli_counts (1 .. 4096; 0 restores the default). */
 int aqc_mps_traj_set_batch(int batch);
 
 /* ---- noisy pair tomography above 24 qubits: aqc_sv_traj_pair_tomo on the MPS engine ---------------
@@ -317,9 +317,45 @@ int aqc_mps_traj_pair_tomo(int n, int chi_cap, double threshold, int max_chi, co
 /* aqc_mps_traj_plan for aqc_mps_traj_pair_tomo's schedule: no measurement rows (counts[5] = 0), the
    last row belongs to the final sort or the flush. */
 int aqc_mps_traj_tomo_plan(int n, const aqc_op_t* prog, int nprog, int* counts, aqc_op_t* sched, int sched_cap);
-/* Debugging: forces the number of states per RDM sweep of aqc_mps_traj_pair_tomo's readout (1 .. 4096,
-   at most the batch; 0 restores the default). */
+/* Debugging: forces the number of states per readout sweep of aqc_mps_traj_pair_tomo (the RDM sweep) and
+   of aqc_mps_traj_pauli_counts (environments, chains, draw) (1 .. 4096, at most the batch; 0 restores
+   the default). */
 int aqc_mps_traj_set_readout_batch(int batch);
+
+/* ---- the noisy Pauli readout above 24 qubits: aqc_sv_traj_pauli_counts on the MPS engine ----------
+   The semantics of aqc_sv_traj_pauli_counts (prog, codes, effects, event numbering, u layout, plus,
+   values and outcomes: see there) on the engine of aqc_mps_traj_pair_tomo.  Trajectory t is an MPS
+   |0...0> of capacity chi_cap with the truncation (threshold, max_chi) and runs
+   aqc_mps_traj_pair_tomo's schedule: gate rows, Kraus rows at the tracked centre, the flush, the sort,
+   no measurement sweep.  For EVERY term j, M_j = (x)_{q in S} D_q with D_q = E[q][c_q - 1][0] -
+   E[q][c_q - 1][1], and v = Re <psi_t|M_j|psi_t> by a transfer chain over the term's support lo..hi
+   between the identity environments L_lo and R_{hi+1}, which assume no canonical form:
+     E = L_lo;  E'[b'][k'] = sum_{s,t} D_i[s][t] conj(A_s[b][b']) E[b][k] A_t[k][k'] for i = lo..hi
+   (D_i = I on a site outside S);  v = Re sum E[b][k] R_{hi+1}[k][b].
+   w = <psi_t|psi_t> by the route of aqc_mps_pauli_expect's all-identity term (L_0, one identity step,
+   R_1).  Neither is divided by the other: p+ = max(0, (w + v) / 2), p- = max(0, (w - v) / 2), and the
+   outcome is 1 (parity -1) iff u (p+ + p-) >= p+, so a truncated trajectory (w < 1) needs no
+   renormalisation.  u = sample_uniform(seed, run, t, E + j); when u is not NULL,
+   u[t (E + nterms) + E + j], host doubles in [0, 1), events first, then terms.
+   plus[j]: host int64, the number of outcome-0 draws.  values: NULL, or nshots x nterms doubles, v.
+   norms: NULL, or nshots doubles, w.  outcomes: NULL, or nshots x nterms bytes.
+   A general factor costs what a Pauli one does: there is no limit on them.
+   The trajectories run in batches of B handles and are read out R at a time (the environments of R
+   states, one chain per (term, state), one draw per (state, term)): R = min(B, 128, what half of 4 GiB
+   less the chains' workspace (at most 512 MiB) hold of the environments, at least 1), B = min(nshots,
+   256, what is left of it hold of handles, at least 1); aqc_mps_traj_set_batch and aqc_mps_traj_set_readout_batch force them.  An
+   outcome depends on (seed, run, t) only -- not on B, R or nshots (fewer shots give a prefix).  Every
+   floating-point sum runs in a fixed order and plus accumulates on the device by integer atomics only
+   (copied back once): two calls return the same bits.
+   AQC_ERR_ARG, before any device call: n outside 1 .. 4096, chi_cap outside 1 .. 1024, nterms outside
+   1 .. 65536, nshots outside 1 .. 2^30, a code above 3, an all-identity term, a malformed or correlated
+   (AQC_OP_KRAUS2) row, the effects check of aqc_sv_traj_pair_tomo, a u outside [0, 1).
+   AQC_ERR_STATE ("capacity (chi_cap) exceeded") when a trajectory outgrows chi_cap: no output is valid
+   then. */
+int aqc_mps_traj_pauli_counts(int n, int chi_cap, double threshold, int max_chi, const aqc_op_t* prog, int nprog,
+                              const uint8_t* codes, int nterms, const double* effects, int nshots, uint64_t seed,
+                              uint64_t run, const double* u, int64_t* plus, double* values, double* norms,
+                              uint8_t* outcomes);
 
 /* ---- Pauli-string expectation values: replaces circuit_operations_pauli_ops.py:60-100 -------------
    (expectation_value_of_pauli_operator, which runs one rotated circuit per term).
