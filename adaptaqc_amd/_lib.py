@@ -46,6 +46,7 @@ EXPORTS = (
     "aqc_env_fallbacks", "aqc_env_set_single", "aqc_env_set_spin_limit",
     "aqc_sv_sample", "aqc_mps_sample", "aqc_sample_uniforms", "aqc_sv_traj_sample",
     "aqc_sv_traj_pair_tomo", "aqc_sv_traj_pauli_counts", "aqc_mps_traj_sample", "aqc_mps_traj_plan", "aqc_mps_traj_set_batch",
+    "aqc_mps_traj_set_correlated",
     "aqc_mps_traj_pair_tomo", "aqc_mps_traj_tomo_plan", "aqc_mps_traj_set_readout_batch", "aqc_mps_traj_pauli_counts",
     "aqc_sv_pauli_expect", "aqc_mps_pauli_expect", "aqc_mps_pauli_expect_batch",
     "aqc_pair_tomo_probs", "aqc_concurrence_bound_probs", "aqc_multinomial_counts", "aqc_tomo_fit",
@@ -163,6 +164,7 @@ _SIGS = {
     "aqc_mps_traj_sample": ([_I, _I, _D, _I, _P, _I, _I, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P], _I),
     "aqc_mps_traj_plan": ([_I, _P, _I, _P, _P, _I], _I),
     "aqc_mps_traj_set_batch": ([_I], _I),
+    "aqc_mps_traj_set_correlated": ([_I], _I),
     "aqc_mps_traj_pair_tomo": ([_I, _I, _D, _I, _P, _I, _P, _I, _P, _I, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P], _I),
     "aqc_mps_traj_tomo_plan": ([_I, _P, _I, _P, _P, _I], _I),
     "aqc_mps_traj_set_readout_batch": ([_I], _I),

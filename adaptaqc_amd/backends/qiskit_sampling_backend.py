@@ -102,24 +102,32 @@ class SamplingSimulator:
     ``mps_pauli_readout`` (needs ``mps_trajectories``): the same rule puts the noisy Pauli readout of
     ``pauli_counts`` on the MPS engine (aqc_mps_traj_pauli_counts: every term read from each trajectory
     by a transfer chain over its support); without it ``pauli_counts`` refuses a noise model there.
-    Opt-in like the other two."""
+    Opt-in like the other two.
+
+    ``mps_correlated`` (needs ``mps_trajectories``): the MPS trajectory engine then takes noise models with
+    correlated two-qubit errors (``depolarizing_error(p, 2)``, ``QuantumError.two_qubit``, two-letter
+    ``pauli_error`` labels) for shots, noisy pair tomography and the noisy Pauli readout; without it those
+    routes refuse such a model by name."""
 
     name = "hip_sampling_simulator"
     METHODS = ("automatic", "statevector", "matrix_product_state")
     MAX_NOISY_QUBITS = 24  # aqc_sv_traj_sample's limit
 
     def __init__(self, method="automatic", seed=None, mps_truncation_threshold=1e-16, max_chi=None,
-                 mps_trajectories=False, mps_pauli_readout=False):
+                 mps_trajectories=False, mps_pauli_readout=False, mps_correlated=False):
         if method not in self.METHODS:
             raise ValueError(f"method must be one of {self.METHODS}")
         if mps_pauli_readout and not mps_trajectories:
             raise ValueError("mps_pauli_readout=True needs mps_trajectories=True")
+        if mps_correlated and not mps_trajectories:
+            raise ValueError("mps_correlated=True needs mps_trajectories=True")
         self.options = SimpleNamespace(method=method, matrix_product_state_truncation_threshold=mps_truncation_threshold,
                                        matrix_product_state_max_bond_dimension=max_chi)
         self.seed = int(seed) if seed is not None else int(np.random.SeedSequence().generate_state(2, np.uint32).view(np.uint64)[0])
         self.runs = 0
         self.mps_trajectories = bool(mps_trajectories)
         self.mps_pauli_readout = bool(mps_pauli_readout)
+        self.mps_correlated = bool(mps_correlated)
         self._last = None  # (n, method, ops bytes, device state)
 
     def __getstate__(self):
@@ -190,12 +198,20 @@ class SamplingSimulator:
                 "'matrix_product_state' with mps_trajectories=True")
         return rows, n_events, "statevector"
 
-    @staticmethod
-    def _refuse_correlated_on_mps(rows):
-        """A program with a correlated two-qubit Kraus group cannot run on the MPS trajectory engine."""
+    def _correlated(self):
+        """Whether the MPS trajectory engine takes correlated groups (absent in an old pickle: no)."""
+        return bool(getattr(self, "mps_correlated", False))
+
+    def _correlated_kw(self):
+        """The keyword that switches the device wrappers' MPS engine to correlated groups, when set."""
+        return {"correlated": True} if self._correlated() else {}
+
+    def _refuse_correlated_on_mps(self, rows):
+        """A program with a correlated two-qubit Kraus group runs on the MPS trajectory engine only with
+        ``mps_correlated``."""
         from ..noise import _CORRELATED_ON_MPS, has_correlated_rows
 
-        if has_correlated_rows(rows):
+        if not self._correlated() and has_correlated_rows(rows):
             raise NotImplementedError(f"noise_model: {_CORRELATED_ON_MPS}")
 
     def _at_learned_capacity(self, n, call):
@@ -221,7 +237,8 @@ class SamplingSimulator:
         from ..device import mps_trajectory_sample
 
         return self._at_learned_capacity(
-            n, lambda **cap: mps_trajectory_sample(n, rows, n_events, shots, seed, run, **cap))
+            n, lambda **cap: mps_trajectory_sample(n, rows, n_events, shots, seed, run,
+                                                   **self._correlated_kw(), **cap))
 
     def run(self, circuit, shots=1024, seed_simulator=None, noise_model=None, **ignored):
         """``noise_model`` (adaptaqc_amd.noise.NoiseModel): every shot is then one quantum trajectory on
@@ -314,7 +331,8 @@ class SamplingSimulator:
             if engine == "statevector":
                 return trajectory_pauli_counts(n, rows, n_events, codes, effects, shots, seed, run)
             return self._at_learned_capacity(
-                n, lambda **cap: mps_trajectory_pauli_counts(n, rows, n_events, codes, effects, shots, seed, run, **cap))
+                n, lambda **cap: mps_trajectory_pauli_counts(n, rows, n_events, codes, effects, shots, seed, run,
+                                                             **self._correlated_kw(), **cap))
         ev = dev.pauli_expect(np.concatenate([codes, np.zeros((1, n), dtype=np.uint8)]))
         v, w = ev[:-1], ev[-1]  # w = <psi|psi>: below 1 for a truncated MPS
         probs = np.stack([np.maximum(0.0, (w + v) / 2), np.maximum(0.0, (w - v) / 2)], axis=1)
@@ -510,7 +528,8 @@ class QiskitSamplingBackend(AQCBackend):
         if engine == "statevector":
             return trajectory_pair_tomography(n, rows, n_events, pairs, effects, shots, seed, run)
         return self.simulator._at_learned_capacity(
-            n, lambda **cap: mps_trajectory_pair_tomography(n, rows, n_events, pairs, effects, shots, seed, run, **cap))
+            n, lambda **cap: mps_trajectory_pair_tomography(n, rows, n_events, pairs, effects, shots, seed, run,
+                                                            **self.simulator._correlated_kw(), **cap))
 
     def _seed_and_run(self, kwargs):
         """(seed, run) of one device sweep: ``seed_simulator`` alone when given, else the

@@ -1627,9 +1627,12 @@ std::vector<std::vector<const DevOp*>> level_ops(const std::vector<DevOp>& ops, 
   std::vector<std::vector<const DevOp*>> lv;
   for (const DevOp& op : ops) {
     int l;
-    if (op.kind == 2) {
+    if (aqc::two_site(op)) {
       l = std::max(last[op.p], last[op.p + 1]) + 1;
       last[op.p] = last[op.p + 1] = l;
+    } else if (op.kind == 5) {  // (a product-unitary group's event: two sites, any distance apart)
+      l = std::max(last[op.p], last[op.p2]) + 1;
+      last[op.p] = last[op.p2] = l;
     } else {
       l = last[op.p] + 1;
       last[op.p] = l;
@@ -1740,9 +1743,9 @@ int aqc::run_waves(aqc_mps_t* hs, int ns, std::vector<std::vector<DevOp>>& lists
   for (int s = 0; s < ns; ++s) {  // every Gamma these lists write (reload bookkeeping)
     int lo = 1 << 30, hi = -1;
     for (const DevOp& op : lists[s]) {
-      lo = std::min(lo, op.p);
-      hi = std::max(hi, op.kind == 2 ? op.p + 1 : op.p);
-      kraus |= op.kind == 3;
+      lo = std::min(lo, op.kind == 5 ? std::min(op.p, op.p2) : op.p);
+      hi = std::max(hi, aqc::two_site(op) ? op.p + 1 : op.kind == 5 ? std::max(op.p, op.p2) : op.p);
+      kraus |= op.kind >= 3;
     }
     if (hi >= 0) hs[s]->changed(lo, hi);
   }
@@ -1765,7 +1768,7 @@ int aqc::run_waves(aqc_mps_t* hs, int ns, std::vector<std::vector<DevOp>>& lists
     int width = 1;
     for (auto& w : lv[s]) {
       int k = 0;
-      for (const DevOp* op : w) k += op->kind == 2;
+      for (const DevOp* op : w) k += aqc::two_site(*op);
       width = std::max(width, k);
     }
     int rc = ensure_slots(hs[s], width);
@@ -1776,7 +1779,9 @@ int aqc::run_waves(aqc_mps_t* hs, int ns, std::vector<std::vector<DevOp>>& lists
   std::vector<TwoSiteJob> two;
   std::vector<OneSiteJob> one;
   std::vector<KrausJob> kr;
-  std::vector<std::pair<size_t, size_t>> two_rng(maxlen), one_rng(maxlen), kr_rng(maxlen);
+  std::vector<aqc::Kraus2Job> k2;       // general group events: theta, then the choice, then the wave's SVD
+  std::vector<aqc::Kraus2ProdJob> kp;   // product-unitary group events
+  std::vector<std::pair<size_t, size_t>> two_rng(maxlen), one_rng(maxlen), kr_rng(maxlen), k2_rng(maxlen), kp_rng(maxlen);
   int cap_max = 0;
   for (int s = 0; s < ns; ++s) cap_max = std::max(cap_max, hs[s]->d.cap);
   // Each two-site job's SVD kernel class from its own largest possible theta side (2 chi): the
@@ -1800,53 +1805,102 @@ int aqc::run_waves(aqc_mps_t* hs, int ns, std::vector<std::vector<DevOp>>& lists
     return std::min(c, 2 * cap_max);
   };
   std::vector<std::pair<int, TwoSiteJob>> wjobs;
+  std::vector<int> wev;  // per wave job: -1, or the general event (index into k2) that acts on its theta
+  std::vector<size_t> idx;
   for (size_t w = 0; w < maxlen; ++w) {
-    size_t t0 = two.size(), o0 = one.size(), k0 = kr.size();
+    size_t t0 = two.size(), o0 = one.size(), k0 = kr.size(), e0 = k2.size(), p0 = kp.size();
     wjobs.clear();
+    wev.clear();
     for (int s = 0; s < ns; ++s) {
       if (w >= lv[s].size()) continue;
       int slot = 0;
       std::vector<int>& ub = hs[s]->ub;
       for (const DevOp* op : lv[s][w]) {
-        if (op->kind == 2) {
+        if (aqc::two_site(*op)) {
           const int p = op->p;
           const int cls = class_of(2 * std::max(ub[p], ub[p + 2]));
           wjobs.push_back({cls, make_two(hs[s], *op, slot++)});
+          wev.push_back(op->kind == 4 ? (int)k2.size() : -1);
+          if (op->kind == 4) k2.push_back({0, op->grp, op->slot, ctx->shot0 + s});
           wjobs.back().second.qr = cls <= 128 ? 1 : 0;
           int nb = std::min(2 * std::min(ub[p], ub[p + 2]), hs[s]->d.cap);
           if (hs[s]->max_chi > 0) nb = std::min(nb, hs[s]->max_chi);
           ub[p + 1] = std::max(nb, 1);
         } else if (op->kind == 3) {
           kr.push_back(make_kraus(hs[s], *op, ctx->shot0 + s));
+        } else if (op->kind == 5) {
+          aqc::Kraus2ProdJob j;
+          std::memset(&j, 0, sizeof(j));
+          j.g0 = hs[s]->d.site(op->p);
+          j.g1 = hs[s]->d.site(op->p2);
+          j.dims0 = hs[s]->d.dims + op->p;
+          j.dims1 = hs[s]->d.dims + op->p2;
+          j.cap = hs[s]->d.cap;
+          j.grp = op->grp;
+          j.slot = op->slot;
+          j.shot = ctx->shot0 + s;
+          kp.push_back(j);
         } else {
           one.push_back(make_one(hs[s], *op));
         }
       }
     }
-    std::stable_sort(wjobs.begin(), wjobs.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
-    for (size_t k = 0; k < wjobs.size(); ++k) {
-      if (k == 0 || wjobs[k].first != wjobs[k - 1].first) wave_cls[w].push_back({wjobs[k].first, two.size(), 0});
-      wave_cls[w].back().count += 1;
-      two.push_back(wjobs[k].second);
+    if (k2.size() == e0) {
+      std::stable_sort(wjobs.begin(), wjobs.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+      for (size_t k = 0; k < wjobs.size(); ++k) {
+        if (k == 0 || wjobs[k].first != wjobs[k - 1].first) wave_cls[w].push_back({wjobs[k].first, two.size(), 0});
+        wave_cls[w].back().count += 1;
+        two.push_back(wjobs[k].second);
+      }
+    } else {
+      // the same order through an index, so that an event learns where its job went: its final place
+      // in the wave is fixed only by this sort
+      idx.resize(wjobs.size());
+      for (size_t k = 0; k < idx.size(); ++k) idx[k] = k;
+      std::stable_sort(idx.begin(), idx.end(), [&](size_t a, size_t b) { return wjobs[a].first < wjobs[b].first; });
+      for (size_t k = 0; k < idx.size(); ++k) {
+        const auto& wj = wjobs[idx[k]];
+        if (k == 0 || wj.first != wjobs[idx[k - 1]].first) wave_cls[w].push_back({wj.first, two.size(), 0});
+        wave_cls[w].back().count += 1;
+        if (wev[idx[k]] >= 0) k2[wev[idx[k]]].two = (int)(two.size() - t0);
+        two.push_back(wj.second);
+      }
     }
     two_rng[w] = {t0, two.size() - t0};
     one_rng[w] = {o0, one.size() - o0};
     kr_rng[w] = {k0, kr.size() - k0};
+    k2_rng[w] = {e0, k2.size() - e0};
+    kp_rng[w] = {p0, kp.size() - p0};
   }
   const size_t tb = two.size() * sizeof(TwoSiteJob), ob = aqc::up256(one.size() * sizeof(OneSiteJob));
-  const size_t kb = kr.size() * sizeof(KrausJob);
+  const size_t gb = k2.size() * sizeof(aqc::Kraus2Job) + kp.size() * sizeof(aqc::Kraus2ProdJob);  // groups
+  const size_t kb = gb ? aqc::up256(kr.size() * sizeof(KrausJob)) : kr.size() * sizeof(KrausJob);
+  const size_t eb = aqc::up256(k2.size() * sizeof(aqc::Kraus2Job));
+  if (gb && !ctx->groups) {
+    aqc::set_error("run_waves: group events without the call's group table");
+    return AQC_ERR_ARG;
+  }
   StagingLease lease(st);
   if (lease.rc() != AQC_OK) return lease.rc();
   aqc::DevScratch& sg = lease.buf();
-  int rc = lease.ensure(tb + ob + kb + 256);
+  int rc = lease.ensure(tb + ob + kb + (gb ? eb + kp.size() * sizeof(aqc::Kraus2ProdJob) : 0) + 256);
   if (rc != AQC_OK) return rc;
   std::memcpy(sg.host, two.data(), tb);
   std::memcpy(sg.host + tb, one.data(), one.size() * sizeof(OneSiteJob));
-  if (kb) std::memcpy(sg.host + tb + ob, kr.data(), kb);
-  if (int e = aqc::upload_async(sg.dev, sg.host, kb ? tb + ob + kb : tb + one.size() * sizeof(OneSiteJob), st)) return e;
+  if (kb) std::memcpy(sg.host + tb + ob, kr.data(), kr.size() * sizeof(KrausJob));
+  if (gb) {
+    if (!k2.empty()) std::memcpy(sg.host + tb + ob + kb, k2.data(), k2.size() * sizeof(aqc::Kraus2Job));
+    if (!kp.empty()) std::memcpy(sg.host + tb + ob + kb + eb, kp.data(), kp.size() * sizeof(aqc::Kraus2ProdJob));
+  }
+  const size_t up = gb   ? tb + ob + kb + eb + kp.size() * sizeof(aqc::Kraus2ProdJob)
+                    : kb ? tb + ob + kb
+                         : tb + one.size() * sizeof(OneSiteJob);
+  if (int e = aqc::upload_async(sg.dev, sg.host, up, st)) return e;
   const TwoSiteJob* dtwo = (const TwoSiteJob*)sg.dev;
   const OneSiteJob* done = (const OneSiteJob*)(sg.dev + tb);
   const KrausJob* dkr = (const KrausJob*)(sg.dev + tb + ob);
+  const aqc::Kraus2Job* dk2 = (const aqc::Kraus2Job*)(sg.dev + tb + ob + kb);
+  const aqc::Kraus2ProdJob* dkp = (const aqc::Kraus2ProdJob*)(sg.dev + tb + ob + kb + eb);
   const int tiles = ((cap_max + 15) / 16) * ((cap_max + 15) / 16);
   const int tiles32 = ((cap_max + 31) / 32) * ((cap_max + 31) / 32);
   const int blocks_split = ((2 * cap_max + 63) / 64) * ((2 * cap_max + 63) / 64);
@@ -1859,6 +1913,8 @@ int aqc::run_waves(aqc_mps_t* hs, int ns, std::vector<std::vector<DevOp>>& lists
     }
     if (kr_rng[w].second)
       if (int e = aqc::launch_kraus(dkr + kr_rng[w].first, (int)kr_rng[w].second, *ctx, st)) return e;
+    if (kp_rng[w].second)
+      if (int e = aqc::launch_kraus2_prod(dkp + kp_rng[w].first, (int)kp_rng[w].second, cap_max, *ctx, st)) return e;
     if (two_rng[w].second) {
       const int nj = (int)two_rng[w].second;
       const TwoSiteJob* jp = dtwo + two_rng[w].first;
@@ -1870,6 +1926,10 @@ int aqc::run_waves(aqc_mps_t* hs, int ns, std::vector<std::vector<DevOp>>& lists
         hipLaunchKernelGGL(k_theta, dim3(aqc::xcd_grid(tiles, nj)), dim3(kT), 0, st, jp, nj);
       aqc::KernelTimer::end(st);
       AQC_CHECK_LAUNCH();
+      // a general group event: its theta stands (G = identity); the operator is chosen from it and
+      // applied to it in place, and the wave's SVD and split then serve it like any other job
+      if (k2_rng[w].second)
+        if (int e = aqc::launch_kraus2(jp, dk2 + k2_rng[w].first, (int)k2_rng[w].second, cap_max, *ctx, st)) return e;
       aqc::KernelTimer::begin(st, "mps_svd", nj * 2.0 * (4.0 * c * c * 16), 0.0);
       for (const ClassRange& cr : wave_cls[w]) {
         const int side = cr.cls, nc = (int)cr.count;

@@ -324,13 +324,21 @@ class StagingLease {
 
 // ---- host-side scheduling (mps.hip; mps_traj.hip builds its schedules with the same types) --------
 struct DevOp {
-  int kind;  // 1: one-site, 2: two-site (p, p+1), 3: one-site Kraus / measurement row (mps_traj.hip)
+  // 1: one-site, 2: two-site (p, p+1), 3: one-site Kraus / measurement row, 4: a correlated group's
+  // event as a two-site update of (p, p+1) whose 4x4 operator is chosen on the device, 5: a
+  // product-unitary group's event on the sites p and p2 (any two; mps_traj.hip)
+  int kind;
   int p;
-  cplx m[16];  // kind 3: the nk 2x2 operators K_k, 4 elements each
+  cplx m[16];  // kind 3: the nk 2x2 operators K_k, 4 elements each; kind 4: the identity (theta's G)
   // kind 3 only.  nk: the number of operators; slot: the row's uniform and output slot -- the event
   // index e of a Kraus row, the qubit q of a measurement row (meas = 1, K = {|0><0|, |1><1|})
-  int nk, slot, meas, pad;
+  // kinds 4 and 5: slot = the event index, grp = the group's place in the call's table (Kraus2Group)
+  int nk, slot, meas, grp;
+  int p2, pad;  // kind 5: the second site
 };
+
+// the rows that run as two-site updates of (p, p+1)
+inline bool two_site(const DevOp& d) { return d.kind == 2 || d.kind == 4; }
 
 // host complex arithmetic without fma(): the x86 host build has no FMA instructions enabled, so
 // fma() is a libm call per operation
@@ -386,19 +394,27 @@ struct Scheduler {
     }
   }
 
-  void two(int qa, int qb, const double* m) {
+  // swap-left routing of (qa, qb) to adjacent sites (low, low + 1); returns low
+  int route(int qa, int qb) {
     const int pa = loc[qa], pb = loc[qb];
     const int low = std::min(pa, pb), high = std::max(pa, pb);
     for (int i = high; i > low + 1; --i) swap_sites(i - 1);  // change_position(high, low+1)
-    cplx M4[16];
-    for (int e = 0; e < 16; ++e) M4[e] = hc(m[2 * e], m[2 * e + 1]);
-    // fold pending one-qubit gates: M' = M . kron(P_b, P_a)   (index 2*b1 + b0, b0 <-> qa)
-    cplx Pa[4] = {hc(1, 0), hc(0, 0), hc(0, 0), hc(1, 0)}, Pb[4] = {hc(1, 0), hc(0, 0), hc(0, 0), hc(1, 0)};
+    return low;
+  }
+
+  // the pending one-qubit gates of qa and qb (the identity where none)
+  void pending(int qa, int qb, cplx* Pa, cplx* Pb) const {
+    for (int e = 0; e < 4; ++e) Pa[e] = Pb[e] = hc(e == 0 || e == 3 ? 1 : 0, 0);
     if (has[qa])
       for (int e = 0; e < 4; ++e) Pa[e] = pend[4 * qa + e];
     if (has[qb])
       for (int e = 0; e < 4; ++e) Pb[e] = pend[4 * qb + e];
-    has[qa] = has[qb] = 0;
+  }
+
+  // M4 (index 2*b1 + b0, b0 <-> qa) with the pending gates Pa, Pb folded in, in the site order of
+  // (low, low + 1) where the routed qubits sit: out[(2 s1' + s2')][(2 s1 + s2)]
+  void fold_site_order(int qa, int low, const cplx* M4, const cplx* Pa, const cplx* Pb, cplx* out16) const {
+    // fold pending one-qubit gates: M' = M . kron(P_b, P_a)   (index 2*b1 + b0, b0 <-> qa)
     cplx K[16];
     for (int r = 0; r < 4; ++r)
       for (int c = 0; c < 4; ++c) K[r * 4 + c] = hmul(Pb[(r >> 1) * 2 + (c >> 1)], Pa[(r & 1) * 2 + (c & 1)]);
@@ -411,9 +427,6 @@ struct Scheduler {
       }
     // to site order: G[(2 s1' + s2')][(2 s1 + s2)]
     const bool a_low = loc[qa] == low;
-    DevOp d = DevOp();
-    d.kind = 2;
-    d.p = low;
     for (int so = 0; so < 4; ++so)
       for (int si = 0; si < 4; ++si) {
         const int s1o = so >> 1, s2o = so & 1, s1i = si >> 1, s2i = si & 1;
@@ -425,8 +438,21 @@ struct Scheduler {
           ro = 2 * s1o + s2o;
           ci = 2 * s1i + s2i;
         }
-        d.m[so * 4 + si] = Mf[ro * 4 + ci];
+        out16[so * 4 + si] = Mf[ro * 4 + ci];
       }
+  }
+
+  void two(int qa, int qb, const double* m) {
+    const int low = route(qa, qb);
+    cplx M4[16];
+    for (int e = 0; e < 16; ++e) M4[e] = hc(m[2 * e], m[2 * e + 1]);
+    cplx Pa[4], Pb[4];
+    pending(qa, qb, Pa, Pb);
+    has[qa] = has[qb] = 0;
+    DevOp d = DevOp();
+    d.kind = 2;
+    d.p = low;
+    fold_site_order(qa, low, M4, Pa, Pb, d.m);
     out.push_back(d);
   }
 
@@ -454,12 +480,46 @@ struct Scheduler {
 // lists handed to run_waves carries shot shot0 + s.  Row slots: Kraus event e -> e, the measurement of
 // qubit q -> nev + q, out of nper = nev + n per shot (aqc_mps_traj_pair_tomo has no measurement rows:
 // nper = nev + npairs, pair j's draw in slot nev + j).
+struct Kraus2Group;
 struct TrajCtx {
   uint64_t seed, run;
   const double* u;   // device: null, or [shot][nper] uniforms replacing sample_uniform(seed, run, shot, slot)
   uint64_t* out;     // device: [shot][words] outcome words, zeroed by the caller (null without measurement rows)
   uint8_t* choices;  // device: null, or [shot][nev]
   int shot0, nev, nper, words;
+  // correlated groups (null / 0 in a call without one): the call's group table, and for the general
+  // events of one wave k_mps_kraus2_rho's partial sums [job][k2_slices][16] and the chosen operator
+  // [job][16]; k2_jobs: the most general events one wave may hold
+  const Kraus2Group* groups;
+  double* k2_part;
+  cplx* k2_sel;
+  int k2_slices, k2_jobs;
+};
+
+// One correlated group of a call, in device memory once per call.  A general group: K[k] the folded
+// 4x4 operator in site order, out 2 s1' + s2', in 2 s1 + s2; W[k] = K_k^dag K_k as M00 M11 M22 M33 then
+// (Re, Im) of M01 M02 M03 M12 M13 M23.  A product-unitary group: K[k][0..3] the 2x2 unitary of the
+// event's site p (the operator's scalar over its modulus folded in), K[k][4..7] that of site p2.
+// flat: every K_k^dag K_k is a multiple of I, the constant weight p_k in W[k][0].
+struct Kraus2Group {
+  cplx K[16][16];
+  double W[16][16];
+  int nk, flat, pad[2];
+};
+
+// One general group event of one state as the k_mps_kraus2_* kernels read it: `two` indexes the
+// wave's two-site jobs, whose theta the event acts on.
+struct Kraus2Job {
+  int two, grp, slot, shot;
+};
+
+// One product-unitary group event of one state (k_mps_kraus2_prod).
+struct Kraus2ProdJob {
+  cplx* g0;  // Gamma of the site of K[k][0..3]
+  cplx* g1;  // Gamma of the site of K[k][4..7]
+  const int* dims0;
+  const int* dims1;
+  int cap, grp, slot, shot;
 };
 
 // One Kraus / measurement row of one state, as k_mps_kraus1 reads it (mps_traj.hip).
@@ -476,6 +536,12 @@ struct KrausJob {
 
 // Queues k_mps_kraus1 over nj device jobs on st (mps_traj.hip).
 int launch_kraus(const KrausJob* jobs, int nj, const TrajCtx& ctx, hipStream_t st);
+// Queues a wave's general group events on st, behind the k_theta launch that formed their thetas
+// (G = identity) and in front of the wave's SVDs: rho in slices, the choice, the chosen operator
+// applied to theta in place (mps_traj.hip).  cap_max: the largest capacity among the jobs.
+int launch_kraus2(const TwoSiteJob* two, const Kraus2Job* jobs, int nj, int cap_max, const TrajCtx& ctx, hipStream_t st);
+// Queues k_mps_kraus2_prod over nj device jobs on st (mps_traj.hip).
+int launch_kraus2_prod(const Kraus2ProdJob* jobs, int nj, int cap_max, const TrajCtx& ctx, hipStream_t st);
 
 // Runs per-state device-op lists in lock-step waves on the MPS stream (mps.hip); returns once the
 // work is queued.  Lists with kind-3 rows need ctx and never take the fused chain.

@@ -15,6 +15,9 @@
 //                                 the SVD is the Schmidt decomposition and the truncation Aer's);
 //                                 then a = a >= p+2 ? a : p+1 and b = b <= p-1 ? b : p
 //   Kraus / measurement row on p  needs a >= p and b <= p; then a = b = p
+//   general group on (p, p+1)     needs what a two-site update needs; then a = p + 1, b = p (the operator
+//                                 is not unitary, so no site beyond the two keeps its property)
+//   product-unitary group         one-site unitaries on two sites: needs nothing, changes nothing
 //   centre moves                  identity-gate two-site updates: on (a, a+1) while a < p, on
 //                                 (b-1, b) while b > the row's right site (b <= a always, so both
 //                                 are legal)
@@ -61,6 +64,7 @@
 #include <vector>
 
 #include "aqc_gemm.h"
+#include "kraus_group.h"
 #include "mps_internal.h"
 #include "pair_draw.h"
 #include "sample_rng.h"
@@ -68,6 +72,10 @@
 using aqc::cplx;
 using aqc::DevOp;
 using aqc::KrausJob;
+using aqc::Kraus2Group;
+using aqc::Kraus2Job;
+using aqc::Kraus2ProdJob;
+using aqc::TwoSiteJob;
 using aqc::TrajCtx;
 
 namespace {
@@ -84,6 +92,11 @@ constexpr size_t kBatchBudgetBytes = (size_t)4 << 30;
 constexpr int kChunkRows = 64;  // schedule rows per run_waves call (bounds the job staging)
 int g_forced_batch = 0;
 int g_forced_readout = 0;  // aqc_mps_traj_set_readout_batch: states per sweep of the pair / Pauli readout
+// aqc_mps_traj_set_correlated: 0 refuses correlated groups, 1 runs them, 2 runs every one as a general group
+int g_correlated = 0;
+constexpr int kK2T = 256;        // threads of the k_mps_kraus2_* kernels (but the one-wave pick)
+constexpr int kRhoSlice = 1024;  // (l, r) positions of theta per workgroup of k_mps_kraus2_rho
+constexpr int kApplyMaxBlocks = 64;
 constexpr int kMaxTerms = 65536;
 constexpr int kCT = 256;  // threads of k_mps_traj_pauli_chain
 constexpr size_t kChainWsBytes = (size_t)512 << 20;  // bound of the chain kernel's E / T workspace
@@ -187,6 +200,210 @@ __global__ __launch_bounds__(kKT) void k_mps_kraus1(const KrausJob* __restrict__
       c.choices[(size_t)local * c.nev + j.slot] = (uint8_t)k;
     }
   }
+}
+
+// ---- correlated two-qubit groups -------------------------------------------------------------
+// A general group event acts on the theta of its two adjacent sites, formed by k_theta with G = I:
+// theta_o[l][r] at theta[(s2 chr + r) M + s1 chl + l], o = 2 s1 + s2, M = 2 chl, carrying all three
+// lambdas.  With the centre condition rho_{oo'} = sum_{l,r} theta_o[l][r] conj(theta_o'[l][r]).
+__device__ __forceinline__ void theta_shape(const TwoSiteJob& j, int& chl, int& chr) {
+  chl = min(j.dims[0], j.cap);
+  chr = min(j.dims[2], j.cap);
+}
+
+__device__ __forceinline__ size_t theta_at(int o, int l, int r, int chl, int chr) {
+  return (size_t)((o & 1) * chr + r) * (size_t)(2 * chl) + (size_t)((o >> 1) * chl + l);
+}
+
+// rho in slices of kRhoSlice positions: grid (slices, jobs).  Each workgroup adds its positions' 16
+// reals (rho_ss, then (Re, Im) of rho_st for s < t in the order 01 02 03 12 13 23) in a fixed order --
+// thread stride, wave butterfly, the waves in index order through the LDS -- and writes them to
+// partial[job][slice]; a slice past theta's end writes zeros.  No atomics.  A flat group (constant
+// weights) needs no rho: its workgroups return at once.
+__global__ __launch_bounds__(kK2T) void k_mps_kraus2_rho(const TwoSiteJob* __restrict__ two,
+                                                         const Kraus2Job* __restrict__ jobs, const TrajCtx c) {
+  __shared__ double red[kK2T / 64][16];
+  const Kraus2Job& e = jobs[blockIdx.y];
+  if (c.groups[e.grp].flat) return;
+  const TwoSiteJob& j = two[e.two];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int chl, chr;
+  theta_shape(j, chl, chr);
+  const int npos = chl * chr, pos0 = (int)blockIdx.x * kRhoSlice;
+  double d[4] = {0.0, 0.0, 0.0, 0.0};  // rho_ss; rho_st = sum a_s conj(a_t), s < t
+  double ox[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, oy[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int q = tid; q < kRhoSlice; q += kK2T) {
+    const int pos = pos0 + q;
+    if (pos >= npos) break;
+    const int l = pos % chl, r = pos / chl;  // (l runs along theta's columns: consecutive addresses)
+    cplx a[4];
+#pragma unroll
+    for (int o = 0; o < 4; ++o) a[o] = aqc::ldg(j.theta + theta_at(o, l, r, chl, chr));
+    int k = 0;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      d[s] += aqc::cnorm2(a[s]);
+#pragma unroll
+      for (int t = s + 1; t < 4; ++t, ++k) {
+        const cplx z = aqc::cmulc(a[s], a[t]);
+        ox[k] += z.x;
+        oy[k] += z.y;
+      }
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < 4; ++s) d[s] = wave_sum(d[s]);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    ox[k] = wave_sum(ox[k]);
+    oy[k] = wave_sum(oy[k]);
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) red[wave][s] = d[s];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      red[wave][4 + 2 * k] = ox[k];
+      red[wave][5 + 2 * k] = oy[k];
+    }
+  }
+  __syncthreads();
+  if (tid < 16) {
+    double x = 0.0;
+    for (int w = 0; w < kK2T / 64; ++w) x += red[w][tid];
+    aqc::stg(c.k2_part + ((size_t)blockIdx.y * c.k2_slices + blockIdx.x) * 16 + tid, x);
+  }
+}
+
+// The smallest k with C_k > u P, else the last k with p_k > 0 (aqc_sv_traj_sample's rule), from the nk
+// clamped weights in pk: every thread that calls it takes the same sums in the same order.
+__device__ __forceinline__ int kraus2_choose(const double* pk, int nk, double u, double& psel) {
+  double P = 0.0;
+  for (int q = 0; q < nk; ++q) P += pk[q];
+  const double target = u * P;
+  int k = -1, lastnz = 0;
+  double cs = 0.0;
+  for (int q = 0; q < nk; ++q) {
+    const double pq = pk[q];
+    cs += pq;
+    if (pq > 0.0) lastnz = q;
+    if (k < 0 && cs > target) k = q;
+  }
+  if (k < 0) k = lastnz;
+  psel = pk[k];
+  return k;
+}
+
+__device__ __forceinline__ double event_uniform(const TrajCtx& c, int shot, int slot) {
+  return c.u ? aqc::ldg(c.u + (size_t)(shot - c.shot0) * c.nper + slot)
+             : aqc::sample_uniform(c.seed, c.run, (uint64_t)shot, (uint32_t)slot);
+}
+
+// One wave per job: the slices summed in index order, p_k = max(0, sum W_k rho) (a flat group: its
+// constant), the choice, the choice byte, and K_k / sqrt(p_k) into the job's slot.
+__global__ __launch_bounds__(64) void k_mps_kraus2_pick(const Kraus2Job* __restrict__ jobs, const TrajCtx c) {
+  __shared__ double rho[16], pkl[16];
+  const Kraus2Job& e = jobs[blockIdx.x];
+  const Kraus2Group& g = c.groups[e.grp];
+  const int tid = threadIdx.x, nk = g.nk, flat = g.flat;
+  if (!flat && tid < 16) {
+    const double* part = c.k2_part + (size_t)blockIdx.x * c.k2_slices * 16 + tid;
+    double x = 0.0;
+    for (int s = 0; s < c.k2_slices; ++s) x += aqc::ldg(part + (size_t)s * 16);
+    rho[tid] = x;
+  }
+  __syncthreads();
+  if (tid < nk) {
+    const double* w = g.W[tid];
+    double p = aqc::ldg(w);
+    if (!flat) {
+      p = p * rho[0] + aqc::ldg(w + 1) * rho[1] + aqc::ldg(w + 2) * rho[2] + aqc::ldg(w + 3) * rho[3];
+      double o = 0.0;
+      for (int q = 4; q < 16; ++q) o += aqc::ldg(w + q) * rho[q];
+      p += 2.0 * o;
+    }
+    pkl[tid] = fmax(0.0, p);
+  }
+  __syncthreads();
+  double psel;
+  const int k = kraus2_choose(pkl, nk, event_uniform(c, e.shot, e.slot), psel);
+  const double sc = psel > 0.0 ? 1.0 / sqrt(psel) : 0.0;
+  if (tid == 0 && c.choices) c.choices[(size_t)(e.shot - c.shot0) * c.nev + e.slot] = (uint8_t)k;
+  if (tid < 16) aqc::stg(c.k2_sel + (size_t)blockIdx.x * 16 + tid, aqc::cscale(aqc::ldg(&g.K[k][tid]), sc));
+}
+
+// theta'_o = sum_i K[o][i] theta_i in place: grid (blocks, jobs), a position's four entries read and
+// written by one thread, so no position waits for another.
+__global__ __launch_bounds__(kK2T) void k_mps_kraus2_apply(const TwoSiteJob* __restrict__ two,
+                                                           const Kraus2Job* __restrict__ jobs, const TrajCtx c) {
+  __shared__ cplx m[16];
+  const TwoSiteJob& j = two[jobs[blockIdx.y].two];
+  if (threadIdx.x < 16) m[threadIdx.x] = aqc::ldg(c.k2_sel + (size_t)blockIdx.y * 16 + threadIdx.x);
+  __syncthreads();
+  int chl, chr;
+  theta_shape(j, chl, chr);
+  const int npos = chl * chr;
+  for (int pos = (int)blockIdx.x * kK2T + (int)threadIdx.x; pos < npos; pos += (int)gridDim.x * kK2T) {
+    const int l = pos % chl, r = pos / chl;
+    cplx v[4];
+#pragma unroll
+    for (int o = 0; o < 4; ++o) v[o] = aqc::ldg(j.theta + theta_at(o, l, r, chl, chr));
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+      cplx acc = aqc::cmul(m[4 * o], v[0]);
+      acc = aqc::cfma(m[4 * o + 1], v[1], acc);
+      acc = aqc::cfma(m[4 * o + 2], v[2], acc);
+      acc = aqc::cfma(m[4 * o + 3], v[3], acc);
+      aqc::stg(j.theta + theta_at(o, l, r, chl, chr), acc);
+    }
+  }
+}
+
+// A product-unitary group's event: grid (blocks, jobs).  The weights are the table's constants, so every
+// workgroup of a job takes the same k from the same arithmetic; then the chosen 2x2 unitary of each of
+// the two sites on that site's Gamma (pass 2 of k_mps_kraus1, twice).  Workgroup 0 writes the choice.
+__global__ __launch_bounds__(kK2T) void k_mps_kraus2_prod(const Kraus2ProdJob* __restrict__ jobs, const TrajCtx c) {
+  const Kraus2ProdJob& j = jobs[blockIdx.y];
+  const Kraus2Group& g = c.groups[j.grp];
+  const int nk = g.nk;
+  double pk[16];
+#pragma unroll
+  for (int q = 0; q < 16; ++q) pk[q] = q < nk ? fmax(0.0, aqc::ldg(&g.W[q][0])) : 0.0;
+  double P = 0.0;
+#pragma unroll
+  for (int q = 0; q < 16; ++q)
+    if (q < nk) P += pk[q];
+  const double target = event_uniform(c, j.shot, j.slot) * P;
+  int k = -1, lastnz = 0;
+  double cs = 0.0;
+#pragma unroll
+  for (int q = 0; q < 16; ++q)
+    if (q < nk) {
+      cs += pk[q];
+      if (pk[q] > 0.0) lastnz = q;
+      if (k < 0 && cs > target) k = q;
+    }
+  if (k < 0) k = lastnz;
+  const int cap = j.cap;
+  const size_t half = (size_t)cap * cap;
+  const int stride = (int)gridDim.x * kK2T, first = (int)blockIdx.x * kK2T + (int)threadIdx.x;
+#pragma unroll
+  for (int site = 0; site < 2; ++site) {
+    const int* dims = site ? j.dims1 : j.dims0;
+    cplx* gam = site ? j.g1 : j.g0;
+    const cplx* m = &g.K[k][4 * site];
+    const cplx m00 = aqc::ldg(m), m01 = aqc::ldg(m + 1), m10 = aqc::ldg(m + 2), m11 = aqc::ldg(m + 3);
+    const int cl = min(dims[0], cap), cr = min(dims[1], cap);
+    for (int e = first; e < cl * cr; e += stride) {
+      const int l = e / cr, r = e - l * cr;
+      const size_t o = (size_t)l * cap + r;
+      const cplx a0 = aqc::ldg(gam + o), a1 = aqc::ldg(gam + half + o);
+      aqc::stg(gam + o, aqc::cfma(m01, a1, aqc::cmul(m00, a0)));
+      aqc::stg(gam + half + o, aqc::cfma(m11, a1, aqc::cmul(m10, a0)));
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0 && c.choices)
+    c.choices[(size_t)(j.shot - c.shot0) * c.nev + j.slot] = (uint8_t)k;
 }
 
 // The pair readout of nr states of a batch: state s of the sweep is trajectory traj0 + s, state
@@ -364,7 +581,9 @@ enum { tGate = 0, tSwap = 1, tMove = 2, tOne = 3, tKraus = 4, tMeas = 5 };
 struct TrajSched {
   std::vector<DevOp> ops;
   std::vector<uint8_t> tag;
+  std::vector<Kraus2Group> groups;  // the correlated groups, in program order (DevOp::grp)
   int nev = 0;
+  int general = 0;  // group events on the general path
 };
 
 thread_local const char* t_entry = "aqc_mps_traj_sample";  // the entry point named in error messages
@@ -395,11 +614,73 @@ int validate(int n, const aqc_op_t* prog, int nprog) {
       }
       if (std::fabs(s00 - 1.0) > 1e-9 || std::fabs(s11 - 1.0) > 1e-9 || std::fabs(sx) > 1e-9 || std::fabs(sy) > 1e-9)
         return fail("Kraus row: sum K^dag K is not the identity");
+    } else if (g_correlated != 0 && (op.flags & 0xff) == AQC_OP_KRAUS2) {
+      // a correlated group, as aqc_sv_traj_sample checks it (kraus_group.h)
+      if (const char* why = aqc::kraus2_first_row_error(op, n, nprog - i)) return fail(why);
+      const int nk = (op.flags >> 16) & 0xff;
+      double w[16][16];
+      bool flat;
+      if (const char* why = aqc::kraus2_group_error(prog + i, nk, w, &flat)) return fail(why);
+      i += nk - 1;
     } else {
       return fail("unknown row flags");
     }
   }
   return AQC_OK;
+}
+
+cplx hdiv(cplx a, cplx b) {  // a / b on the host
+  const double d = b.x * b.x + b.y * b.y;
+  return aqc::hc((a.x * b.x + a.y * b.y) / d, (a.y * b.x - a.x * b.y) / d);
+}
+
+// K (4x4, index 2 b1 + b0) = z B (x) A with A (on b0) and B (on b1) unitary, all within 1e-12: then A
+// times z / |z| into A, B into B.  The zero operator qualifies (A = B = I; its weight is 0).
+bool product_unitary(const double* m, cplx* A, cplx* B) {
+  cplx K[16];
+  int at = 0;
+  double big = 0.0;
+  for (int e = 0; e < 16; ++e) {
+    K[e] = aqc::hc(m[2 * e], m[2 * e + 1]);
+    const double v = K[e].x * K[e].x + K[e].y * K[e].y;
+    if (v > big) big = v, at = e;
+  }
+  for (int e = 0; e < 4; ++e) A[e] = B[e] = aqc::hc(e == 0 || e == 3 ? 1 : 0, 0);
+  if (std::sqrt(big) <= 1e-12) return true;
+  const int r = at >> 2, c = at & 3, r1 = r >> 1, r0 = r & 1, c1 = c >> 1, c0 = c & 1;
+  const cplx z = K[at];
+  cplx A0[4], B0[4];  // z B[r1][c1] A and z A[r0][c0] B
+  for (int i = 0; i < 2; ++i)
+    for (int j = 0; j < 2; ++j) {
+      A0[2 * i + j] = K[(2 * r1 + i) * 4 + 2 * c1 + j];
+      B0[2 * i + j] = K[(2 * i + r0) * 4 + 2 * j + c0];
+    }
+  for (int i = 0; i < 2; ++i)
+    for (int j = 0; j < 2; ++j)
+      for (int k = 0; k < 2; ++k)
+        for (int l = 0; l < 2; ++l) {
+          const cplx t = hdiv(aqc::hmul(B0[2 * i + j], A0[2 * k + l]), z), want = K[(2 * i + k) * 4 + 2 * j + l];
+          if (std::hypot(t.x - want.x, t.y - want.y) > 1e-12) return false;
+        }
+  auto unit = [](cplx* U) {  // U / sqrt(alpha) where U^dag U = alpha I; false where it is not
+    const double alpha = U[0].x * U[0].x + U[0].y * U[0].y + U[2].x * U[2].x + U[2].y * U[2].y;
+    if (!(alpha > 0.0)) return -1.0;
+    const double sc = 1.0 / std::sqrt(alpha);
+    for (int e = 0; e < 4; ++e) U[e] = aqc::hc(U[e].x * sc, U[e].y * sc);
+    const double n1 = U[1].x * U[1].x + U[1].y * U[1].y + U[3].x * U[3].x + U[3].y * U[3].y;
+    // column 0 . column 1
+    const double dx = U[0].x * U[1].x + U[0].y * U[1].y + U[2].x * U[3].x + U[2].y * U[3].y;
+    const double dy = U[0].x * U[1].y - U[0].y * U[1].x + U[2].x * U[3].y - U[2].y * U[3].x;
+    if (std::fabs(n1 - 1.0) > 1e-12 || std::fabs(dx) > 1e-12 || std::fabs(dy) > 1e-12) return -1.0;
+    return alpha;
+  };
+  const double alpha = unit(A0), beta = unit(B0);
+  if (alpha < 0.0 || beta < 0.0) return false;
+  // K = B0 (x) A0 / z = (sqrt(alpha beta) / z) B (x) A: the scalar's phase is conj(z) / |z|
+  const double az = std::sqrt(big);
+  const cplx ph = aqc::hc(z.x / az, -z.y / az);
+  for (int e = 0; e < 4; ++e) A[e] = aqc::hmul(ph, A0[e]), B[e] = B0[e];
+  return true;
 }
 
 struct Planner {
@@ -465,6 +746,67 @@ struct Planner {
     a = b = p;
   }
 
+  // A correlated group on (q0, q1): one event.  Product-unitary (every K_k a scalar times A_k (x) B_k,
+  // both unitary; not under mode 2): constant weights and one-site unitaries, which keep both
+  // orthonormality properties -- one row on the two sites where the qubits sit, no routing, no centre
+  // move, no SVD.  Otherwise a two-site update whose 4x4 operator is chosen on the device: routed and
+  // folded like a gate (Scheduler::two), behind the centre moves of a two-site update; the split of
+  // theta' is then a Schmidt decomposition, and the centre stands on the two sites (a = p + 1, b = p).
+  void group(const aqc_op_t* ops, int nk) {
+    const int q0 = ops[0].q0, q1 = ops[0].q1;
+    double w[16][16];
+    bool flat = true;
+    aqc::kraus2_group_error(ops, nk, w, &flat);  // (validated: only the weights are wanted)
+    Kraus2Group g;
+    std::memset(&g, 0, sizeof(g));
+    g.nk = nk;
+    g.flat = flat ? 1 : 0;
+    cplx A[16][4], B[16][4], Pa[4], Pb[4];
+    bool product = flat && g_correlated != 2;
+    for (int k = 0; k < nk && product; ++k) product = product_unitary(ops[k].m, A[k], B[k]);
+    DevOp d = DevOp();
+    d.nk = nk;
+    d.slot = out.nev++;
+    d.grp = (int)out.groups.size();
+    if (product) {
+      sc.pending(q0, q1, Pa, Pb);
+      sc.has[q0] = sc.has[q1] = 0;
+      for (int k = 0; k < nk; ++k) {
+        aqc::mat2_mul(A[k], Pa, &g.K[k][0]);
+        aqc::mat2_mul(B[k], Pb, &g.K[k][4]);
+        g.W[k][0] = w[k][0];
+      }
+      d.kind = 5;
+      d.p = loc[q0];
+      d.p2 = loc[q1];
+      push(d, tKraus);
+    } else {
+      const int low = sc.route(q0, q1);
+      drain(false);
+      sc.pending(q0, q1, Pa, Pb);
+      sc.has[q0] = sc.has[q1] = 0;
+      for (int k = 0; k < nk; ++k) {
+        cplx M4[16];
+        for (int e = 0; e < 16; ++e) M4[e] = aqc::hc(ops[k].m[2 * e], ops[k].m[2 * e + 1]);
+        sc.fold_site_order(q0, low, M4, Pa, Pb, g.K[k]);
+        aqc::kraus2_weights((const double*)g.K[k], g.W[k]);
+        if (flat) g.W[k][0] = w[k][0];  // the constant weight by aqc_sv_traj_sample's own arithmetic
+      }
+      centre(low, low + 1);
+      d.kind = 4;
+      d.p = low;
+      for (int e = 0; e < 4; ++e) d.m[5 * e] = aqc::hc(1, 0);
+      // K_k is not unitary: the Schmidt values of every other bond change, so nothing beyond the two
+      // sites keeps its property (a gate's update keeps a >= p + 2 and b <= p - 1); the split leaves
+      // site p left- and site p + 1 right-orthonormal
+      push(d, tKraus);
+      a = low + 1;
+      b = low;
+      out.general += 1;
+    }
+    out.groups.push_back(g);
+  }
+
   // measure: the sweep of measurement rows behind the sort (the sampler's ending; the pair readout
   // stops at the sorted state)
   void run(const aqc_op_t* prog, int nprog, bool measure) {
@@ -479,6 +821,10 @@ struct Planner {
           sc.has[q] = 0;
         }
         row(loc[q], nk, K, out.nev++, 0);
+      } else if ((op.flags & 0xff) == AQC_OP_KRAUS2) {
+        const int nk = (op.flags >> 16) & 0xff;
+        group(prog + i, nk);
+        i += nk - 1;
       } else if (op.nq == 1) {
         sc.one(op.q0, op.m);
       } else {
@@ -511,11 +857,14 @@ int max_width(const DevOp* ops, size_t count, int n) {
   for (size_t i = 0; i < count; ++i) {
     const DevOp& op = ops[i];
     int l;
-    if (op.kind == 2) {
+    if (aqc::two_site(op)) {
       l = std::max(last[op.p], last[op.p + 1]) + 1;
       last[op.p] = last[op.p + 1] = l;
       if ((int)per.size() <= l) per.resize(l + 1, 0);
       width = std::max(width, ++per[l]);
+    } else if (op.kind == 5) {
+      l = std::max(last[op.p], last[op.p2]) + 1;
+      last[op.p] = last[op.p2] = l;
     } else {
       l = last[op.p] + 1;
       last[op.p] = l;
@@ -545,12 +894,50 @@ struct Handles {
 
 // device bytes of one trajectory's handle while the schedule runs: the Gammas, and one two-site
 // workspace per concurrent update of the widest wave of a chunk
-size_t evolve_state_bytes(const TrajSched& sch, int n, size_t cap) {
+int sched_width(const TrajSched& sch, int n) {
   const size_t nrows = sch.ops.size();
   int width = 1;
   for (size_t r0 = 0; r0 < nrows; r0 += kChunkRows)
     width = std::max(width, max_width(sch.ops.data() + r0, std::min<size_t>(kChunkRows, nrows - r0), n));
+  return width;
+}
+
+size_t evolve_state_bytes(const TrajSched& sch, int n, size_t cap) {
+  const int width = sched_width(sch, n);
   return ((size_t)n * 2 * cap * cap + (size_t)width * (4 * cap * cap + aqc::work_elems(cap))) * sizeof(cplx);
+}
+
+// What a call with correlated groups keeps on the device beside its states: the group table, and for the
+// general events of one wave (at most one per two-site update of the widest wave and state) the partial
+// sums of k_mps_kraus2_rho and the chosen operators.
+struct K2Bufs {
+  size_t gb = 0, pb = 0, sb = 0;
+  int slices = 0, jobs = 0;
+  size_t bytes() const { return gb + pb + sb; }
+};
+
+K2Bufs k2_bufs(const TrajSched& sch, int n, int B, int cap) {
+  K2Bufs k;
+  if (sch.groups.empty()) return k;
+  k.gb = up256(sch.groups.size() * sizeof(Kraus2Group));
+  if (sch.general == 0) return k;
+  k.slices = (int)(((size_t)cap * cap + kRhoSlice - 1) / kRhoSlice);
+  k.jobs = B * sched_width(sch, n);
+  k.pb = up256((size_t)k.jobs * k.slices * 16 * sizeof(double));
+  k.sb = up256((size_t)k.jobs * 16 * sizeof(cplx));
+  return k;
+}
+
+// binds the buffers at `base` (k.bytes() of device memory) and queues the table's upload
+int k2_bind(const TrajSched& sch, const K2Bufs& k, char* base, TrajCtx& ctx, hipStream_t st) {
+  if (k.gb == 0) return AQC_OK;
+  ctx.groups = (const Kraus2Group*)base;
+  ctx.k2_part = k.pb ? (double*)(base + k.gb) : nullptr;
+  ctx.k2_sel = k.sb ? (cplx*)(base + k.gb + k.pb) : nullptr;
+  ctx.k2_slices = k.slices;
+  ctx.k2_jobs = k.jobs;
+  AQC_HIP_CHECK(hipMemcpyAsync(base, sch.groups.data(), sch.groups.size() * sizeof(Kraus2Group), hipMemcpyHostToDevice, st));
+  return AQC_OK;
 }
 
 // The schedule's rows on nb states (state s carrying shot ctx.shot0 + s), chunk by chunk; then waits
@@ -565,31 +952,62 @@ int run_rows(const TrajSched& sch, aqc_mps_t* hs, int nb, const TrajCtx& ctx, st
   return aqc_mps_check_batch(hs, nb);
 }
 
-// aqc_mps_traj_plan's output of a schedule
+// aqc_mps_traj_plan's output of a schedule: a row per DevOp, a group's event as its nk rows
 void write_plan(const TrajSched& s, int* counts, aqc_op_t* sched, int sched_cap) {
   for (int c = 0; c < 7; ++c) counts[c] = 0;
   for (uint8_t t : s.tag) counts[t] += 1;
-  counts[6] = (int)s.ops.size();
-  const size_t nout = std::min<size_t>(s.ops.size(), (size_t)sched_cap);
-  for (size_t i = 0; i < nout; ++i) {
-    const DevOp& d = s.ops[i];
-    aqc_op_t& o = sched[i];
-    std::memset(&o, 0, sizeof(o));
-    o.q0 = d.p;
+  size_t at = 0;
+  auto next = [&]() -> aqc_op_t* {
+    aqc_op_t* o = at < (size_t)sched_cap ? &sched[at] : nullptr;
+    ++at;
+    if (o) std::memset(o, 0, sizeof(*o));
+    return o;
+  };
+  for (const DevOp& d : s.ops) {
+    if (d.kind == 4 || d.kind == 5) {
+      const Kraus2Group& g = s.groups[d.grp];
+      const bool swapped = d.kind == 5 && d.p2 < d.p;  // the row's q0 is the lower site, s1 its index
+      for (int k = 0; k < d.nk; ++k) {
+        aqc_op_t* o = next();
+        if (!o) continue;
+        o->nq = 2;
+        o->q0 = d.kind == 4 ? d.p : std::min(d.p, d.p2);
+        o->q1 = d.kind == 4 ? d.p + 1 : std::max(d.p, d.p2);
+        o->flags = AQC_OP_KRAUS2 | (k << 8) | (d.nk << 16) | (d.kind == 5 ? 1 << 24 : 0);
+        if (d.kind == 4) {
+          std::memcpy(o->m, g.K[k], 16 * sizeof(cplx));
+        } else {  // sqrt(p_k) U_lower (x) U_upper, out 2 s1' + s2', in 2 s1 + s2
+          const cplx* lo = &g.K[k][swapped ? 4 : 0];
+          const cplx* hi = &g.K[k][swapped ? 0 : 4];
+          const double sc = std::sqrt(std::max(0.0, g.W[k][0]));
+          cplx* m = (cplx*)o->m;
+          for (int so = 0; so < 4; ++so)
+            for (int si = 0; si < 4; ++si) {
+              const cplx t = aqc::hmul(lo[(so >> 1) * 2 + (si >> 1)], hi[(so & 1) * 2 + (si & 1)]);
+              m[so * 4 + si] = aqc::hc(t.x * sc, t.y * sc);
+            }
+        }
+      }
+      continue;
+    }
+    aqc_op_t* o = next();
+    if (!o) continue;
+    o->q0 = d.p;
     if (d.kind == 2) {
-      o.nq = 2;
-      o.q1 = d.p + 1;
-      std::memcpy(o.m, d.m, 16 * sizeof(cplx));
+      o->nq = 2;
+      o->q1 = d.p + 1;
+      std::memcpy(o->m, d.m, 16 * sizeof(cplx));
     } else if (d.kind == 1) {
-      o.nq = 1;
-      std::memcpy(o.m, d.m, 4 * sizeof(cplx));
+      o->nq = 1;
+      std::memcpy(o->m, d.m, 4 * sizeof(cplx));
     } else {
-      o.nq = 1;
-      o.q1 = d.meas ? d.slot : d.nk;
-      o.flags = d.meas ? AQC_OP_MEASURE1 : (AQC_OP_KRAUS1 | (d.slot << 8));
-      std::memcpy(o.m, d.m, 4 * (size_t)d.nk * sizeof(cplx));
+      o->nq = 1;
+      o->q1 = d.meas ? d.slot : d.nk;
+      o->flags = d.meas ? AQC_OP_MEASURE1 : (AQC_OP_KRAUS1 | (d.slot << 8));
+      std::memcpy(o->m, d.m, 4 * (size_t)d.nk * sizeof(cplx));
     }
   }
+  counts[6] = (int)at;
 }
 
 int plan(const char* entry, bool measure, int n, const aqc_op_t* prog, int nprog, int* counts, aqc_op_t* sched,
@@ -615,7 +1033,50 @@ int aqc::launch_kraus(const KrausJob* jobs, int nj, const TrajCtx& ctx, hipStrea
   return AQC_OK;
 }
 
+int aqc::launch_kraus2(const TwoSiteJob* two, const Kraus2Job* jobs, int nj, int cap_max, const TrajCtx& ctx,
+                       hipStream_t st) {
+  if (!(ctx.groups && ctx.k2_part && ctx.k2_sel) || nj > ctx.k2_jobs ||
+      ((size_t)cap_max * cap_max + kRhoSlice - 1) / kRhoSlice > (size_t)ctx.k2_slices) {
+    aqc::set_error("launch_kraus2: the trajectory context has no room for the wave's group events");
+    return AQC_ERR_ARG;
+  }
+  const double pos = (double)cap_max * cap_max;
+  // rho: theta read once; apply: read and written
+  KernelTimer::begin(st, "mps_kraus2_rho", nj * pos * 4.0 * 16.0, nj * pos * 64.0);
+  hipLaunchKernelGGL(k_mps_kraus2_rho, dim3(ctx.k2_slices, nj), dim3(kK2T), 0, st, two, jobs, ctx);
+  KernelTimer::end(st);
+  AQC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_mps_kraus2_pick, dim3(nj), dim3(64), 0, st, jobs, ctx);
+  AQC_CHECK_LAUNCH();
+  const int blocks = (int)std::min<size_t>(kApplyMaxBlocks, ((size_t)cap_max * cap_max + kK2T - 1) / kK2T);
+  KernelTimer::begin(st, "mps_kraus2_apply", nj * pos * 8.0 * 16.0, nj * pos * 128.0);
+  hipLaunchKernelGGL(k_mps_kraus2_apply, dim3(blocks, nj), dim3(kK2T), 0, st, two, jobs, ctx);
+  KernelTimer::end(st);
+  AQC_CHECK_LAUNCH();
+  return AQC_OK;
+}
+
+int aqc::launch_kraus2_prod(const Kraus2ProdJob* jobs, int nj, int cap_max, const TrajCtx& ctx, hipStream_t st) {
+  if (!ctx.groups) {
+    aqc::set_error("launch_kraus2_prod: the trajectory context has no group table");
+    return AQC_ERR_ARG;
+  }
+  const int blocks = (int)std::min<size_t>(kApplyMaxBlocks, ((size_t)cap_max * cap_max + kK2T - 1) / kK2T);
+  // each job: two sites' Gammas read and written
+  KernelTimer::begin(st, "mps_kraus2_prod", nj * 8.0 * 16.0 * (double)cap_max * cap_max, 0.0);
+  hipLaunchKernelGGL(k_mps_kraus2_prod, dim3(blocks, nj), dim3(kK2T), 0, st, jobs, ctx);
+  KernelTimer::end(st);
+  AQC_CHECK_LAUNCH();
+  return AQC_OK;
+}
+
 extern "C" {
+
+int aqc_mps_traj_set_correlated(int mode) {
+  AQC_REQUIRE(mode >= 0 && mode <= 2, "aqc_mps_traj_set_correlated: 0 (refuse), 1 (run) or 2 (every group general)");
+  g_correlated = mode;
+  return AQC_OK;
+}
 
 int aqc_mps_traj_set_batch(int batch) {
   AQC_REQUIRE(batch >= 0 && batch <= 4096, "aqc_mps_traj_set_batch: 0 (default) or 1 .. 4096");
@@ -661,9 +1122,10 @@ int aqc_mps_traj_sample(int n, int chi_cap, double threshold, int max_chi, const
   const size_t ub = u ? up256((size_t)B * nper * sizeof(double)) : 0;
   const size_t ob = up256((size_t)B * words * sizeof(uint64_t));
   const size_t cb = want_choices ? up256((size_t)B * nev) : 0;
+  const K2Bufs k2 = k2_bufs(sch, n, B, chi_cap);
   AQC_HIP_CHECK(hipStreamSynchronize(st));  // (the scratch may be regrown)
   aqc::DevScratch& scr = g_scr.here();
-  if (int rc = scr.ensure(ub + ob + cb)) return rc;
+  if (int rc = scr.ensure(ub + ob + cb + k2.bytes())) return rc;
   TrajCtx ctx;
   std::memset(&ctx, 0, sizeof(ctx));
   ctx.seed = seed;
@@ -674,6 +1136,7 @@ int aqc_mps_traj_sample(int n, int chi_cap, double threshold, int max_chi, const
   ctx.nev = nev;
   ctx.nper = nper;
   ctx.words = words;
+  if (int rc = k2_bind(sch, k2, scr.dev + ub + ob + cb, ctx, st)) return rc;
   std::vector<std::vector<DevOp>> lists;
   for (int shot0 = 0; shot0 < nshots; shot0 += B) {
     const int nb = std::min(B, nshots - shot0);
@@ -748,9 +1211,10 @@ int aqc_mps_traj_pair_tomo(int n, int chi_cap, double threshold, int max_chi, co
   const size_t tb = up256((size_t)npairs * 36 * sizeof(int64_t));
   const size_t ob = outcomes ? up256((size_t)B * npairs) : 0;
   const size_t rb = up256((size_t)R * npairs * 16 * sizeof(cplx));
+  const K2Bufs k2 = k2_bufs(sch, n, B, chi_cap);
   AQC_HIP_CHECK(hipStreamSynchronize(st));  // (the scratch may be regrown)
   aqc::DevScratch& scr = g_scr.here();
-  if (int rc = scr.ensure(ub + qb + eb + tb + ob + rb)) return rc;
+  if (int rc = scr.ensure(ub + qb + eb + tb + ob + rb + k2.bytes())) return rc;
   char* buf = scr.dev;
   TrajCtx ctx;
   std::memset(&ctx, 0, sizeof(ctx));
@@ -759,6 +1223,7 @@ int aqc_mps_traj_pair_tomo(int n, int chi_cap, double threshold, int max_chi, co
   ctx.u = u ? (const double*)buf : nullptr;
   ctx.nev = nev;
   ctx.nper = nper;
+  if (int rc = k2_bind(sch, k2, buf + ub + qb + eb + tb + ob + rb, ctx, st)) return rc;
   PairDrawJob dj;
   std::memset(&dj, 0, sizeof(dj));
   dj.u = ctx.u;
@@ -896,9 +1361,11 @@ int aqc_mps_traj_pauli_counts(int n, int chi_cap, double threshold, int max_chi,
   const size_t ob = outcomes ? up256((size_t)B * nterms) : 0;
   const size_t sb = up256((size_t)R * sizeof(ChainState));
   const size_t rb = up256((size_t)R * nout * sizeof(double));
+  const K2Bufs k2 = k2_bufs(sch, n, B, chi_cap);
   AQC_HIP_CHECK(hipStreamSynchronize(st));  // (the scratch may be regrown)
   aqc::DevScratch& scr = g_scr.here();
-  if (int rc = scr.ensure(ub + cb + tb + db + pb + vb + nb8 + ob + sb + rb + (size_t)nwg * per_wg)) return rc;
+  if (int rc = scr.ensure(ub + cb + tb + db + pb + vb + nb8 + ob + sb + rb + up256((size_t)nwg * per_wg) + k2.bytes()))
+    return rc;
   char* at = scr.dev;
   auto take = [&](size_t bytes) {
     char* p = at;
@@ -934,8 +1401,9 @@ int aqc_mps_traj_pauli_counts(int n, int chi_cap, double threshold, int max_chi,
   dj.nper = nper;
   cj.states = (const ChainState*)take(sb);
   cj.out = (double*)take(rb);
-  cj.ws = (cplx*)take((size_t)nwg * per_wg);
+  cj.ws = (cplx*)take(up256((size_t)nwg * per_wg));
   dj.vals = cj.out;
+  if (int rc = k2_bind(sch, k2, take(k2.bytes()), ctx, st)) return rc;
   AQC_HIP_CHECK(hipMemcpyAsync((void*)cj.codes, codes, (size_t)nterms * n, hipMemcpyHostToDevice, st));
   AQC_HIP_CHECK(hipMemcpyAsync((void*)cj.terms, terms.data(), terms.size() * sizeof(int), hipMemcpyHostToDevice, st));
   AQC_HIP_CHECK(hipMemcpyAsync((void*)cj.dtab, dtab.data(), dtab.size() * sizeof(double), hipMemcpyHostToDevice, st));

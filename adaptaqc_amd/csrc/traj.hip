@@ -62,6 +62,7 @@
 #include <vector>
 
 #include "aqc_internal.h"
+#include "kraus_group.h"
 #include "pair_draw.h"
 #include "sample_rng.h"
 
@@ -572,14 +573,11 @@ int fail(const std::string& msg) {
 // the nk rows of a correlated group whose first row (k = 0, nk, qubits) has been checked: every row's
 // flags and qubits, finite entries, M_k = K_k^dag K_k into w, sum M_k = I within 1e-9
 int build_group(const aqc_op_t* ops, int nk, TrajRow* out, int ev) {
-  double sum[16] = {0.0};
+  double w[16][16];
   bool flat = true;
+  if (const char* why = aqc::kraus2_group_error(ops, nk, w, &flat)) return fail(why);
   for (int k = 0; k < nk; ++k) {
     const aqc_op_t& op = ops[k];
-    if (op.flags != (AQC_OP_KRAUS2 | (k << 8) | (nk << 16)) || op.nq != 2 || op.q0 != ops[0].q0 || op.q1 != ops[0].q1)
-      return fail("malformed Kraus group: rows k = 0 .. nk-1 in order on the same qubits");
-    for (int e = 0; e < 32; ++e)
-      if (!std::isfinite(op.m[e])) return fail("malformed Kraus group: a matrix entry is not finite");
     TrajRow& r = out[k];
     r.kind = kKraus2;
     r.q0 = op.q0;
@@ -588,31 +586,8 @@ int build_group(const aqc_op_t* ops, int nk, TrajRow* out, int ev) {
     r.ev = ev;
     r.k = k;
     std::memcpy(r.m, op.m, 32 * sizeof(double));
-    // M_st = sum_r conj(K_rs) K_rt; K_rs = m[2 (4 r + s)] + i m[2 (4 r + s) + 1]
-    int c = 0;
-    for (int s = 0; s < 4; ++s)
-      for (int t = s; t < 4; ++t) {
-        double x = 0.0, y = 0.0;
-        for (int q = 0; q < 4; ++q) {
-          const double ar = op.m[2 * (4 * q + s)], ai = op.m[2 * (4 * q + s) + 1];
-          const double br = op.m[2 * (4 * q + t)], bi = op.m[2 * (4 * q + t) + 1];
-          x += ar * br + ai * bi;
-          y += ar * bi - ai * br;
-        }
-        if (t == s) {
-          r.w[s] = x;
-          sum[s] += x;
-          if (std::fabs(x - r.w[0]) > 1e-12) flat = false;
-        } else {
-          r.w[4 + 2 * c] = x, r.w[5 + 2 * c] = y;
-          sum[4 + 2 * c] += x, sum[5 + 2 * c] += y;
-          if (std::fabs(x) > 1e-12 || std::fabs(y) > 1e-12) flat = false;
-          ++c;
-        }
-      }
+    std::memcpy(r.w, w[k], sizeof(r.w));
   }
-  for (int e = 0; e < 16; ++e)
-    if (std::fabs(sum[e] - (e < 4 ? 1.0 : 0.0)) > 1e-9) return fail("Kraus group: sum K^dag K is not the identity");
   out[0].flat = flat ? 1 : 0;
   return AQC_OK;
 }
@@ -656,9 +631,7 @@ int build_rows(int n, const aqc_op_t* prog, int nprog, std::vector<TrajRow>& row
         return fail("Kraus row: sum K^dag K is not the identity");
     } else if ((op.flags & 0xff) == AQC_OP_KRAUS2) {
       const int nk = (op.flags >> 16) & 0xff;
-      if (op.flags != (AQC_OP_KRAUS2 | (nk << 16)) || nk < 1 || nk > 16 || nk > nprog - i)
-        return fail("malformed Kraus group: its first row needs k = 0 and 1 .. 16 operators within the program");
-      if (op.q0 < 0 || op.q0 >= n || op.q1 < 0 || op.q1 >= n || op.q0 == op.q1) return fail("Kraus group: bad qubits");
+      if (const char* why = aqc::kraus2_first_row_error(op, n, nprog - i)) return fail(why);
       if (int rc = build_group(prog + i, nk, &rows[i], ev++)) return rc;
       i += nk - 1;
     } else {

@@ -289,6 +289,38 @@ def _refuse_correlated_rows(rows, what):
         raise NotImplementedError(f"{what}: {_CORRELATED_ON_MPS}")
 
 
+class _correlated_mode:
+    """The MPS trajectory engine's process-wide switch for correlated groups (aqc_mps_traj_set_correlated)
+    around one call: ``correlated`` False / 0 leaves it alone (the refusal stands), True / 1 runs groups,
+    2 runs every group on the general path.  0 is restored on exit."""
+
+    def __init__(self, correlated):
+        self.mode = int(correlated)
+        if self.mode not in (0, 1, 2):
+            raise ValueError("correlated must be False, True (1) or 2")
+
+    def __enter__(self):
+        if self.mode:
+            _lib.check(_lib.load().aqc_mps_traj_set_correlated(self.mode))
+        return self
+
+    def __exit__(self, *exc):
+        if self.mode:
+            _lib.load().aqc_mps_traj_set_correlated(0)
+        return False
+
+
+def _check_mps_rows(rows, n_events, correlated, what):
+    """The refusal of correlated groups unless ``correlated``, and n_events against the program."""
+    if not int(correlated):
+        _refuse_correlated_rows(rows, what)
+        found = int(np.count_nonzero(rows["flags"] == _lib.OP_KRAUS1))
+    else:
+        found = _count_events(rows)
+    if found != n_events:
+        raise ValueError(f"{what}: n_events does not match the program's Kraus rows")
+
+
 def trajectory_sample(n, rows, n_events, shots, seed, run=0, u=None, return_choices=False):
     """``shots`` noisy shots as quantum trajectories (aqc_sv_traj_sample): uint64[shots] basis indices
     (bit q = qubit q) of the program ``rows`` (noise.trajectory_program) on n qubits, whose events
@@ -374,7 +406,7 @@ def trajectory_pauli_counts(n, rows, n_events, terms, effects, shots, seed, run=
 
 
 def mps_trajectory_sample(n, rows, n_events, shots, seed, run=0, u=None, return_choices=False, chi_cap=64,
-                          threshold=1e-16, max_chi=None):
+                          threshold=1e-16, max_chi=None, correlated=False):
     """``shots`` noisy shots as quantum trajectories on the MPS engine (aqc_mps_traj_sample):
     uint64[shots, (n + 63) // 64] outcome words (bit q % 64 of word q // 64 = qubit q, DeviceMPS.sample's
     format) of the program ``rows`` (noise.trajectory_program) on n qubits, whose Kraus rows number
@@ -382,35 +414,35 @@ def mps_trajectory_sample(n, rows, n_events, shots, seed, run=0, u=None, return_
     ``max_chi``); one that outgrows the capacity raises the capacity AqcError.  ``u``: [shots,
     n_events + n] uniforms in [0, 1) used instead of the generator's (event e in column e, qubit q's
     measurement in column n_events + q).  With ``return_choices`` also the uint8[shots, n_events] Kraus
-    operator chosen at every event."""
+    operator chosen at every event.  ``correlated``: False refuses a program with correlated two-qubit
+    groups; True (or 1) runs them, one event each (choices 0 .. 15), a product-unitary group such as
+    ``depolarizing_error(p, 2)`` as one-site unitaries and any other as a two-site update whose operator is
+    chosen on the device; 2 sends every group down that general path (a second route to the same outcomes)."""
     shots, n_events, n = int(shots), int(n_events), int(n)
     rows = np.ascontiguousarray(rows, dtype=_lib.OP_DTYPE)
-    _refuse_correlated_rows(rows, "mps_trajectory_sample")
-    if int(np.count_nonzero(rows["flags"] == _lib.OP_KRAUS1)) != n_events:
-        raise ValueError("mps_trajectory_sample: n_events does not match the program's Kraus rows")
+    _check_mps_rows(rows, n_events, correlated, "mps_trajectory_sample")
     out = np.zeros((max(shots, 0), (max(n, 1) + 63) // 64), dtype=np.uint64)
     up = _uniforms_arg(u, (shots, n_events + n))
     choices = np.zeros((max(shots, 0), n_events), dtype=np.uint8) if return_choices else None
-    _lib.check(_lib.lib().aqc_mps_traj_sample(n, int(chi_cap), float(threshold), int(max_chi or 0),
-                                              _lib.ptr(rows) if len(rows) else None, len(rows), shots, _u64(seed),
-                                              _u64(run), _lib.ptr(up), _lib.ptr(out),
-                                              _lib.ptr(choices) if return_choices and n_events else None))
+    with _correlated_mode(correlated):
+        _lib.check(_lib.lib().aqc_mps_traj_sample(n, int(chi_cap), float(threshold), int(max_chi or 0),
+                                                  _lib.ptr(rows) if len(rows) else None, len(rows), shots, _u64(seed),
+                                                  _u64(run), _lib.ptr(up), _lib.ptr(out),
+                                                  _lib.ptr(choices) if return_choices and n_events else None))
     return (out, choices) if return_choices else out
 
 
 def mps_trajectory_pair_tomography(n, rows, n_events, pairs, effects, shots, seed, run=0, u=None, return_outcomes=False,
-                                   chi_cap=64, threshold=1e-16, max_chi=None):
+                                   chi_cap=64, threshold=1e-16, max_chi=None, correlated=False):
     """``trajectory_pair_tomography`` on the MPS engine (aqc_mps_traj_pair_tomo): the same arguments, the
     same int64 [npairs, 9, 4] counts and, with ``return_outcomes``, uint8 [9 shots, npairs] outcomes.
     Every one of the 9 ``shots`` trajectories is an MPS of capacity ``chi_cap`` truncated by
     (``threshold``, ``max_chi``), run through ``mps_trajectory_sample``'s schedule without its
     measurement sweep and read out pair by pair from its RDMs; one that outgrows the capacity raises
-    the capacity AqcError."""
+    the capacity AqcError.  ``correlated``: as ``mps_trajectory_sample``."""
     n, shots, n_events = int(n), int(shots), int(n_events)
     rows = np.ascontiguousarray(rows, dtype=_lib.OP_DTYPE)
-    _refuse_correlated_rows(rows, "mps_trajectory_pair_tomography")
-    if int(np.count_nonzero(rows["flags"] == _lib.OP_KRAUS1)) != n_events:
-        raise ValueError("mps_trajectory_pair_tomography: n_events does not match the program's Kraus rows")
+    _check_mps_rows(rows, n_events, correlated, "mps_trajectory_pair_tomography")
     pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
     npairs = len(pr)
     eff = np.ascontiguousarray(effects, dtype=np.float64)
@@ -420,16 +452,18 @@ def mps_trajectory_pair_tomography(n, rows, n_events, pairs, effects, shots, see
     up = _uniforms_arg(u, (ntraj, n_events + npairs))
     counts = np.zeros((npairs, 9, 4), dtype=np.int64)
     outcomes = np.zeros((ntraj, npairs), dtype=np.uint8) if return_outcomes else None
-    _lib.check(_lib.lib().aqc_mps_traj_pair_tomo(n, int(chi_cap), float(threshold), int(max_chi or 0),
-                                                 _lib.ptr(rows) if len(rows) else None, len(rows),
-                                                 _lib.ptr(pr) if npairs else None, npairs, _lib.ptr(eff), shots,
-                                                 _u64(seed), _u64(run), _lib.ptr(up), _lib.ptr(counts),
-                                                 _lib.ptr(outcomes) if return_outcomes and npairs else None))
+    with _correlated_mode(correlated):
+        _lib.check(_lib.lib().aqc_mps_traj_pair_tomo(n, int(chi_cap), float(threshold), int(max_chi or 0),
+                                                     _lib.ptr(rows) if len(rows) else None, len(rows),
+                                                     _lib.ptr(pr) if npairs else None, npairs, _lib.ptr(eff), shots,
+                                                     _u64(seed), _u64(run), _lib.ptr(up), _lib.ptr(counts),
+                                                     _lib.ptr(outcomes) if return_outcomes and npairs else None))
     return (counts, outcomes) if return_outcomes else counts
 
 
 def mps_trajectory_pauli_counts(n, rows, n_events, terms, effects, shots, seed, run=0, u=None, return_values=False,
-                                return_norms=False, return_outcomes=False, chi_cap=64, threshold=1e-16, max_chi=None):
+                                return_norms=False, return_outcomes=False, chi_cap=64, threshold=1e-16, max_chi=None,
+                                correlated=False):
     """``trajectory_pauli_counts`` on the MPS engine (aqc_mps_traj_pauli_counts): the same arguments and
     the same int64 [nterms] count of +1 parities, with no limit on the general factors of a term.  Every
     one of the ``shots`` trajectories is an MPS of capacity ``chi_cap`` truncated by (``threshold``,
@@ -439,14 +473,12 @@ def mps_trajectory_pauli_counts(n, rows, n_events, terms, effects, shots, seed, 
     ``return_norms`` the float64 [shots] w = <psi_t|psi_t> (below 1 for a truncated trajectory; the draw
     uses p+- = (w +- v) / 2, so nothing is renormalised), with ``return_outcomes`` the uint8
     [shots, nterms] outcomes (1 = parity -1); the result is then the tuple
-    (plus[, values][, norms][, outcomes])."""
+    (plus[, values][, norms][, outcomes]).  ``correlated``: as ``mps_trajectory_sample``."""
     from . import paulis
 
     n, shots, n_events = int(n), int(shots), int(n_events)
     rows = np.ascontiguousarray(rows, dtype=_lib.OP_DTYPE)
-    _refuse_correlated_rows(rows, "mps_trajectory_pauli_counts")
-    if int(np.count_nonzero(rows["flags"] == _lib.OP_KRAUS1)) != n_events:
-        raise ValueError("mps_trajectory_pauli_counts: n_events does not match the program's Kraus rows")
+    _check_mps_rows(rows, n_events, correlated, "mps_trajectory_pauli_counts")
     codes = paulis.terms_to_codes(terms, n)
     nterms = len(codes)
     eff = np.ascontiguousarray(effects, dtype=np.float64)
@@ -457,13 +489,14 @@ def mps_trajectory_pauli_counts(n, rows, n_events, terms, effects, shots, seed, 
     values = np.zeros((max(shots, 0), nterms)) if return_values else None
     norms = np.zeros(max(shots, 0)) if return_norms else None
     outcomes = np.zeros((max(shots, 0), nterms), dtype=np.uint8) if return_outcomes else None
-    _lib.check(_lib.lib().aqc_mps_traj_pauli_counts(n, int(chi_cap), float(threshold), int(max_chi or 0),
-                                                    _lib.ptr(rows) if len(rows) else None, len(rows),
-                                                    _lib.ptr(codes) if nterms else None, nterms, _lib.ptr(eff), shots,
-                                                    _u64(seed), _u64(run), _lib.ptr(up), _lib.ptr(plus),
-                                                    _lib.ptr(values) if return_values and nterms else None,
-                                                    _lib.ptr(norms) if return_norms and shots > 0 else None,
-                                                    _lib.ptr(outcomes) if return_outcomes and nterms else None))
+    with _correlated_mode(correlated):
+        _lib.check(_lib.lib().aqc_mps_traj_pauli_counts(n, int(chi_cap), float(threshold), int(max_chi or 0),
+                                                        _lib.ptr(rows) if len(rows) else None, len(rows),
+                                                        _lib.ptr(codes) if nterms else None, nterms, _lib.ptr(eff), shots,
+                                                        _u64(seed), _u64(run), _lib.ptr(up), _lib.ptr(plus),
+                                                        _lib.ptr(values) if return_values and nterms else None,
+                                                        _lib.ptr(norms) if return_norms and shots > 0 else None,
+                                                        _lib.ptr(outcomes) if return_outcomes and nterms else None))
     out = ((plus,) + ((values,) if return_values else ()) + ((norms,) if return_norms else ())
            + ((outcomes,) if return_outcomes else ()))
     return out if len(out) > 1 else plus
@@ -473,25 +506,30 @@ MPS_TRAJECTORY_COUNTS = ("gate_updates", "swap_updates", "centre_moves", "one_si
                          "measure_rows", "rows")
 
 
-def mps_trajectory_plan(n, rows, return_schedule=False, measure=True):
+def mps_trajectory_plan(n, rows, return_schedule=False, measure=True, correlated=False):
     """The site-level schedule every shot of ``mps_trajectory_sample`` runs (aqc_mps_traj_plan; no GPU):
     a dict of the row counts named in MPS_TRAJECTORY_COUNTS (a two-site update is a gate, swap or
     centre-move row), and with ``return_schedule`` also the rows themselves as an OP_DTYPE array
     (``q0`` the site; flags 0 unitary, ``flags & 0xff == OP_KRAUS1`` a Kraus row with its event index
     in ``flags >> 8``, OP_MEASURE1 the measurement of qubit ``q1``; see include/aqc_hip.h).
     ``measure=False``: the schedule of ``mps_trajectory_pair_tomography`` (aqc_mps_traj_tomo_plan), which
-    ends with the sort, before the measurement sweep."""
+    ends with the sort, before the measurement sweep.
+    ``correlated`` (as ``mps_trajectory_sample``): a group's event then appears as nk consecutive rows with
+    ``flags == OP_KRAUS2 | k << 8 | nk << 16``, bit 24 added for a product-unitary group, ``q0 < q1`` the
+    two sites and ``m`` the folded operator in site order; "kraus_rows" counts a group once."""
     rows = np.ascontiguousarray(rows, dtype=_lib.OP_DTYPE)
-    _refuse_correlated_rows(rows, "mps_trajectory_plan")
+    if not int(correlated):
+        _refuse_correlated_rows(rows, "mps_trajectory_plan")
     counts = np.zeros(7, dtype=np.int32)
     prog = _lib.ptr(rows) if len(rows) else None
     entry = _lib.load().aqc_mps_traj_plan if measure else _lib.load().aqc_mps_traj_tomo_plan
-    _lib.check(entry(int(n), prog, len(rows), _lib.ptr(counts), None, 0))
-    named = dict(zip(MPS_TRAJECTORY_COUNTS, (int(c) for c in counts)))
-    if not return_schedule:
-        return named
-    sched = np.zeros(int(counts[6]), dtype=_lib.OP_DTYPE)
-    _lib.check(entry(int(n), prog, len(rows), _lib.ptr(counts), _lib.ptr(sched), len(sched)))
+    with _correlated_mode(correlated):
+        _lib.check(entry(int(n), prog, len(rows), _lib.ptr(counts), None, 0))
+        named = dict(zip(MPS_TRAJECTORY_COUNTS, (int(c) for c in counts)))
+        if not return_schedule:
+            return named
+        sched = np.zeros(int(counts[6]), dtype=_lib.OP_DTYPE)
+        _lib.check(entry(int(n), prog, len(rows), _lib.ptr(counts), _lib.ptr(sched), len(sched)))
     return named, sched
 
 

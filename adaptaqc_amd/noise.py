@@ -17,16 +17,23 @@ that of the channel; the individual trajectories depend on the Kraus decompositi
 A correlated error follows a two-qubit gate as one event: one of its 1-16 4x4 operators is drawn with
 probability |K_k psi|^2 and applied to both qubits (matrix index 2 b(second listed qubit) + b(first
 listed qubit), a two-qubit gate row's and Aer's convention).  It runs on the statevector trajectory
-engine (up to 24 qubits); the MPS trajectory engine refuses it by name.
+engine (up to 24 qubits), and on the MPS trajectory engine where the caller opts in
+(``SamplingSimulator(..., mps_trajectories=True, mps_correlated=True)``, ``correlated=True`` on the
+``device.mps_trajectory_*`` wrappers); without the opt-in the MPS routes refuse it by name.  There a
+product-unitary error (every operator a scalar times a product of two unitaries: every Pauli channel,
+``depolarizing_error(p, 2)``) costs two one-site updates and no SVD; any other is a two-site update whose
+operator is chosen on the device from the pair's reduced density matrix.
 
-Out of scope: correlated errors on the MPS engine, two errors on one instruction, readout-error
-matrices, reset, errors on gates of three or more qubits.
+Out of scope: two errors on one instruction, readout-error matrices, reset, errors on gates of three or
+more qubits.
 """
 import numpy as np
 
 _TOL = 1e-9
-_CORRELATED_ON_MPS = ("correlated two-qubit errors run on the statevector trajectory engine only (at most 24 "
-                      "qubits): the MPS trajectory engine does not support them yet")
+_CORRELATED_ON_MPS = ("correlated two-qubit errors run on the statevector trajectory engine (at most 24 qubits) "
+                      "unless the MPS trajectory engine is told to take them: build the simulator with "
+                      "mps_trajectories=True, mps_correlated=True, or pass correlated=True to the "
+                      "device.mps_trajectory_* call")
 _PAULIS = {
     "I": np.eye(2, dtype=complex),
     "X": np.array([[0, 1], [1, 0]], dtype=complex),

@@ -180,7 +180,8 @@ int aqc_mps_sample(aqc_mps_t h, int nshots, uint64_t seed, uint64_t run, const d
    group's operators (p_k = |K_k psi|^2 = Re Tr(K_k^dag K_k rho) with rho the 4x4 reduced density
    matrix of (q0, q1); where every K_k^dag K_k is a multiple of I within 1e-12, as for Pauli channels,
    p_k is that multiple), and choices holds k = 0 .. 15.  aqc_sv_traj_sample and
-   aqc_sv_traj_pair_tomo take such rows; the MPS entry points answer AQC_ERR_ARG for them.
+   aqc_sv_traj_pair_tomo take such rows; the MPS entry points answer AQC_ERR_ARG for them unless
+   aqc_mps_traj_set_correlated has switched them on.
    AQC_ERR_ARG, before any device call, also for a malformed group: k not running 0 .. nk-1 over
    consecutive rows, nk outside 1 .. 16, differing qubits inside a group, q0 = q1 or a qubit out of
    range, an entry that is not finite, sum K^dag K off the identity by more than 1e-9. */
@@ -267,6 +268,20 @@ int aqc_sv_traj_pauli_counts(int n, const aqc_op_t* prog, int nprog, const uint8
    The shots run in batches of B trajectories held as B internal MPS handles: B = min(nshots, 256,
    what 4 GiB of device memory hold of them, at least 1).  A shot's result depends on (seed, run, shot)
    only, not on B; no atomics in any reduction: two calls return the same bits.
+   A correlated group (AQC_OP_KRAUS2 rows; only under aqc_mps_traj_set_correlated(1 or 2), else
+   AQC_ERR_ARG) is one event with the semantics of aqc_sv_traj_sample: p_k = Re Tr(K_k^dag K_k rho) with
+   rho the 4x4 RDM of (q0, q1), the constant multiple where every K_k^dag K_k is one (by the same host
+   arithmetic), the same choice rule, choices k = 0 .. 15, the same check of malformed groups before any
+   device call.  It runs one of two ways.  General: the two qubits are routed to adjacent sites like a
+   gate's, the pending one-qubit gates folded in (K_k <- K_k (P_q1 (x) P_q0)), the centre brought to the
+   two sites; theta of the two sites is contracted once, rho_{oo'} = sum_{l,r} theta_o[l][r]
+   conj(theta_o'[l][r]) (o = 2 s1 + s2) summed in fixed slices of 1024 (l, r) positions, the operator
+   chosen and K_k / sqrt(p_k) applied to theta in place, and theta' split by the engine's SVD as after
+   any two-site update; the centre then stands on the two sites.  Product-unitary -- every K_k a scalar times A_k (x) B_k with both factors
+   unitary within 1e-12 (every Pauli channel, the two-qubit depolarizing error): the weights are
+   constants and the operators one-site unitaries, so k is drawn from the constants and the chosen A_k,
+   B_k (pending gates folded in) act on the two sites where the qubits sit, adjacent or not, with no
+   routing, no centre move and no SVD.
    AQC_ERR_ARG as aqc_sv_traj_sample (n < 1, a malformed row, sum K^dag K off the identity by more
    than 1e-9, a u outside [0, 1), nshots outside 1 .. 2^30).  AQC_ERR_STATE ("capacity (chi_cap)
    exceeded") when any trajectory outgrows chi_cap: no part of the output is valid then. */
@@ -280,13 +295,25 @@ int aqc_mps_traj_sample(int n, int chi_cap, double threshold, int max_chi, const
    carrying the identity); nq = 1: a flushed one-qubit gate.  (flags & 0xff) == AQC_OP_KRAUS1: a Kraus
    row, q1 operators in m after folding, the event index in flags >> 8.  flags == AQC_OP_MEASURE1: the
    measurement of qubit q1 (= q0, the qubits being sorted), m = {|0><0|, |1><1|}.
+   (flags & 0xff) == AQC_OP_KRAUS2 (under aqc_mps_traj_set_correlated): a group's event as nk
+   consecutive rows, nq = 2, flags = AQC_OP_KRAUS2 | k << 8 | nk << 16, q0 < q1 the two sites and m the
+   folded K_k in site order (index 2 s_q0 + s_q1).  A general group: q1 = q0 + 1, and the event counts as
+   a two-site update of those sites.  A product-unitary group adds bit 24 to flags; its sites need not be
+   adjacent and it moves neither the centre nor a qubit.  Events are numbered in row order, a group
+   taking one number.
    counts[7]: gate updates, routing / sorting swap updates, centre-move updates, one-site unitary
-   rows, Kraus rows, measurement rows, all rows. */
+   rows, Kraus events (one-qubit rows and groups, one per group), measurement rows, all rows. */
 #define AQC_OP_MEASURE1 2
 int aqc_mps_traj_plan(int n, const aqc_op_t* prog, int nprog, int* counts, aqc_op_t* sched, int sched_cap);
 /* Debugging: forces the batch size B of aqc_mps_traj_sample, aqc_mps_traj_pair_tomo and
    aqc_mps_traj_pauli_counts (1 .. 4096; 0 restores the default). */
 int aqc_mps_traj_set_batch(int batch);
+/* Correlated two-qubit groups (AQC_OP_KRAUS2 rows) on the MPS trajectory engine, process-wide like
+   aqc_mps_traj_set_batch.  0 (default): aqc_mps_traj_plan, aqc_mps_traj_tomo_plan, aqc_mps_traj_sample,
+   aqc_mps_traj_pair_tomo and aqc_mps_traj_pauli_counts answer AQC_ERR_ARG for such a row.  1: they take
+   groups.  2: as 1 with every group on the general path, product-unitary ones included (debugging: a
+   second route to the same outcomes).  AQC_ERR_ARG outside 0 .. 2. */
+int aqc_mps_traj_set_correlated(int mode);
 
 /* ---- noisy pair tomography above 24 qubits: aqc_sv_traj_pair_tomo on the MPS engine ---------------
    The semantics of aqc_sv_traj_pair_tomo (pairs, effects, settings, draw rule, u layout, counts and
@@ -294,7 +321,8 @@ int aqc_mps_traj_set_batch(int batch);
    MPS |0...0> of capacity chi_cap with the truncation (threshold, max_chi); trajectory t = 9 i + s
    serves setting s of EVERY pair.  A trajectory runs aqc_mps_traj_sample's schedule without the
    measurement sweep: gate rows, Kraus rows at the tracked centre (same event numbering, choice rule
-   and folding K_k <- K_k P), then the flush of pending one-qubit gates and the sort.  For pair j, rho is
+   and folding K_k <- K_k P; correlated groups as there, under aqc_mps_traj_set_correlated), then the
+   flush of pending one-qubit gates and the sort.  For pair j, rho is
    the 4x4 RDM of the trajectory's MPS (index 2 bit_hi + bit_lo) by the full contraction of
    aqc_mps_pair_rdms_batch, which assumes no canonical form (a Kraus row breaks Vidal form);
    p_o = max(0, Re Tr[(E[hi][b_hi][o_hi] (x) E[lo][b_lo][o_lo]) rho]), and one outcome by
@@ -348,8 +376,9 @@ int aqc_mps_traj_set_readout_batch(int batch);
    floating-point sum runs in a fixed order and plus accumulates on the device by integer atomics only
    (copied back once): two calls return the same bits.
    AQC_ERR_ARG, before any device call: n outside 1 .. 4096, chi_cap outside 1 .. 1024, nterms outside
-   1 .. 65536, nshots outside 1 .. 2^30, a code above 3, an all-identity term, a malformed or correlated
-   (AQC_OP_KRAUS2) row, the effects check of aqc_sv_traj_pair_tomo, a u outside [0, 1).
+   1 .. 65536, nshots outside 1 .. 2^30, a code above 3, an all-identity term, a malformed row, a
+   correlated (AQC_OP_KRAUS2) row unless aqc_mps_traj_set_correlated allows it (then a malformed group,
+   as aqc_mps_traj_sample), the effects check of aqc_sv_traj_pair_tomo, a u outside [0, 1).
    AQC_ERR_STATE ("capacity (chi_cap) exceeded") when a trajectory outgrows chi_cap: no output is valid
    then. */
 int aqc_mps_traj_pauli_counts(int n, int chi_cap, double threshold, int max_chi, const aqc_op_t* prog, int nprog,
