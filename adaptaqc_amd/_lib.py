@@ -18,6 +18,12 @@ OP_DTYPE = np.dtype(
     [("nq", "<i4"), ("q0", "<i4"), ("q1", "<i4"), ("flags", "<i4"), ("m", "<f8", (32,))], align=True
 )
 assert OP_DTYPE.itemsize == 272
+# aqc_dm_step_t: a step of aqc_dm_plan
+DM_STEP_DTYPE = np.dtype(
+    [("kind", "<i4"), ("nq", "<i4"), ("q0", "<i4"), ("q1", "<i4"), ("segment", "<i4"), ("pad", "<i4", (3,)),
+     ("m", "<f8", (512,))], align=True
+)
+assert DM_STEP_DTYPE.itemsize == 4128
 OP_KRAUS1 = 1  # AQC_OP_KRAUS1: a Kraus row of aqc_sv_traj_sample / aqc_mps_traj_sample
 OP_MEASURE1 = 2  # AQC_OP_MEASURE1: a measurement row of aqc_mps_traj_plan's schedule
 OP_KRAUS2 = 3  # AQC_OP_KRAUS2: one operator of a correlated two-qubit Kraus group (flags | k << 8 | nk << 16)
@@ -50,6 +56,8 @@ EXPORTS = (
     "aqc_mps_traj_pair_tomo", "aqc_mps_traj_tomo_plan", "aqc_mps_traj_set_readout_batch", "aqc_mps_traj_pauli_counts",
     "aqc_sv_pauli_expect", "aqc_mps_pauli_expect", "aqc_mps_pauli_expect_batch",
     "aqc_pair_tomo_probs", "aqc_concurrence_bound_probs", "aqc_multinomial_counts", "aqc_tomo_fit",
+    "aqc_dm_create", "aqc_dm_destroy", "aqc_dm_reset", "aqc_dm_apply", "aqc_dm_plan", "aqc_dm_get", "aqc_dm_trace0",
+    "aqc_dm_diag_sv", "aqc_dm_pauli_expect", "aqc_dm_pair_rdms",
 )
 
 
@@ -177,6 +185,16 @@ _SIGS = {
     "aqc_concurrence_bound_probs": ([_P, _I, _P, _I], _I),
     "aqc_multinomial_counts": ([_P, _I, _I, _I, ctypes.c_uint64, ctypes.c_uint64, _P, _P], _I),
     "aqc_tomo_fit": ([_P, _I, _P, _I], _I),
+    "aqc_dm_create": ([_I, ctypes.POINTER(_P)], _I),
+    "aqc_dm_destroy": ([_P], _I),
+    "aqc_dm_reset": ([_P], _I),
+    "aqc_dm_apply": ([_P, _P, _I], _I),
+    "aqc_dm_plan": ([_I, _P, _I, _P, _P, _I], _I),
+    "aqc_dm_get": ([_P, _P], _I),
+    "aqc_dm_trace0": ([_P, _P], _I),
+    "aqc_dm_diag_sv": ([_P, _P], _I),
+    "aqc_dm_pauli_expect": ([_P, _P, _I, _P, _P], _I),
+    "aqc_dm_pair_rdms": ([_P, _P, _I, _P], _I),
 }
 
 

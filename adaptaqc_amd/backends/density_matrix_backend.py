@@ -1,0 +1,213 @@
+"""Exact noisy simulation on MI355X: the density-matrix engine (csrc/dm.hip) as a simulator handle and
+as a compiler backend.
+
+What ``QiskitSamplingBackend`` estimates from shots under ``execute_kwargs["noise_model"]`` -- every
+shot one quantum trajectory -- the density matrix gives exactly: one deterministic evolution of rho by
+the same flat program (``noise.trajectory_program``) yields the noisy cost 1 - rho_00, every qubit's
+<Z>, every pair's reduced density matrix, every Pauli term and the whole outcome distribution.  Up to
+``MAX_QUBITS`` = 13 qubits (4^13 complex128 is 1 GiB); above that the trajectory engines
+(``SamplingSimulator``: statevector trajectories to 24 qubits, MPS trajectories beyond) are the route.
+
+* ``DensityMatrixSimulator``: a stand-in for an Aer simulator handle with ``method="density_matrix"``,
+  with ``SamplingSimulator``'s ``run`` / ``pauli_counts`` contracts: the shots are drawn from the exact
+  distribution, so ``QiskitSamplingBackend(DensityMatrixSimulator(), ...)`` works as it is.
+* ``DensityMatrixBackend``: an ``AQCBackend`` without shots -- the expectation of the sampling
+  backend's costs, and ISL from the exact mixed RDMs (``pair_rdms``).
+"""
+import numpy as np
+
+from .aqc_backend import AQCBackend
+from .qiskit_sampling_backend import (SamplingJob, SamplingResult, terminal_measurements,
+                                      without_classical_operations)
+
+MAX_QUBITS = 13  # aqc_dm_create's limit
+
+
+def _refuse_width(n, who):
+    if n > MAX_QUBITS:
+        raise NotImplementedError(
+            f"{who}: the density matrix stops at {MAX_QUBITS} qubits ({n} asked for): run a noise model on the "
+            "trajectory engines instead -- SamplingSimulator (statevector trajectories up to 24 qubits, MPS "
+            "trajectories with mps_trajectories=True above)")
+
+
+class _Evolved:
+    """rho after a program, kept on the device and keyed by the program's bytes."""
+
+    def __init__(self):
+        self._last = None  # (n, program bytes, DeviceDM)
+
+    def state(self, n, rows):
+        from ..device import DeviceDM
+
+        key = rows.tobytes()
+        if self._last is not None and self._last[:2] == (n, key):
+            return self._last[2]
+        dev = self._last[2] if self._last is not None and self._last[0] == n else None
+        self._last = None
+        if dev is None:
+            dev = DeviceDM(n)
+        else:
+            dev.reset()
+        dev.run(rows)
+        self._last = (n, key, dev)
+        return dev
+
+
+class DensityMatrixSimulator:
+    """Stand-in for an Aer simulator handle with ``method="density_matrix"``.
+
+    ``run(circuit, shots=1024, seed_simulator=None, noise_model=None)`` evolves rho once by the circuit's
+    program under ``noise_model`` (cached, keyed by the program's bytes) and draws ``shots`` outcomes of
+    its measurements from the diagonal on the device; ``result().get_counts()`` follows
+    ``SamplingSimulator.run``: keys over the classical bits (highest leftmost; over all qubits without
+    measure instructions), an unmeasured bit reads 0, and with ``seed_simulator`` the shots depend on
+    that seed alone, else on the simulator's seed and a run counter that every call advances."""
+
+    name = "hip_density_matrix_simulator"
+    MAX_QUBITS = MAX_QUBITS
+
+    def __init__(self, seed=None):
+        self.seed = int(seed) if seed is not None else int(np.random.SeedSequence().generate_state(2, np.uint32).view(np.uint64)[0])
+        self.runs = 0
+        self._evolved = _Evolved()
+
+    def __getstate__(self):
+        d = dict(self.__dict__)
+        d["_evolved"] = _Evolved()
+        return d
+
+    def __repr__(self):
+        return "DensityMatrixSimulator(hip, gfx950)"
+
+    def _state(self, circuit, noise_model):
+        from ..noise import trajectory_program
+
+        n = circuit.num_qubits
+        _refuse_width(n, "DensityMatrixSimulator")
+        rows, _, _ = trajectory_program(circuit, noise_model)
+        return self._evolved.state(n, rows)
+
+    def _seed_and_run(self, seed_simulator):
+        if seed_simulator is not None:
+            return int(seed_simulator), 0
+        seed, run = self.seed, self.runs
+        self.runs += 1
+        return seed, run
+
+    def run(self, circuit, shots=1024, seed_simulator=None, noise_model=None, **ignored):
+        from ..device import counts_from_samples
+
+        measured = terminal_measurements(circuit)
+        dev = self._state(circuit, noise_model)
+        seed, run = self._seed_and_run(seed_simulator)
+        samples = dev.sample(int(shots), seed, run)
+        counts = counts_from_samples(samples, circuit.num_qubits, measured)
+        if measured is not None:  # keys over every classical bit: an unmeasured one reads 0
+            width = max(int(getattr(circuit, "num_clbits", 0) or 0), max(measured.values()) + 1)
+            counts = {k.rjust(width, "0"): v for k, v in counts.items()}
+        return SamplingJob(SamplingResult(counts))
+
+    def _values(self, circuit, codes, noise_model):
+        """Tr(M_t rho) / Tr rho of the noisy readout of every term: the circuit without its classical
+        operations, the errors on the appended ``sdg`` / ``h`` / ``measure`` as POVM effects."""
+        from ..noise import readout_effects
+
+        n = circuit.num_qubits
+        dev = self._state(without_classical_operations(circuit), noise_model)
+        effects = readout_effects(n, noise_model) if noise_model is not None else None
+        return dev.pauli_expect(codes, effects) / dev.trace()
+
+    def pauli_values(self, circuit, labels, noise_model=None):
+        """float64 [len(labels)]: the exact expectation of the +-1 parity that the reference's rotated and
+        measured copy of ``circuit`` reads for every Pauli label (qiskit order) under ``noise_model`` --
+        what ``pauli_counts`` estimates; without a model, <P>.  An all-identity label gives 1."""
+        from ..paulis import terms_to_codes
+
+        codes = terms_to_codes(list(labels), circuit.num_qubits)
+        out = np.ones(len(codes))
+        live = codes.any(axis=1) if len(codes) else np.zeros(0, dtype=bool)
+        if live.any():
+            out[live] = self._values(circuit, np.ascontiguousarray(codes[live]), noise_model)
+        return out
+
+    def pauli_counts(self, circuit, labels, shots=1024, seed_simulator=None, noise_model=None):
+        """int64 [len(labels)]: ``SamplingSimulator.pauli_counts``'s contract -- for every label (none
+        all-identity) the number of +1 parities among ``shots`` shots.  The value of every term is exact
+        (``pauli_values``); its count is one binomial draw on the device (aqc_multinomial_counts), so
+        different terms are independent.  Seed and run counter as ``run``."""
+        from ..device import multinomial_counts
+        from ..paulis import terms_to_codes
+
+        shots = int(shots)
+        codes = terms_to_codes(list(labels), circuit.num_qubits)
+        if len(codes) == 0:
+            return np.zeros(0, dtype=np.int64)
+        if not codes.any(axis=1).all():
+            raise ValueError("pauli_counts: an all-identity label has the value 1 and is not measured")
+        v = self._values(circuit, codes, noise_model)
+        seed, run = self._seed_and_run(seed_simulator)
+        probs = np.stack([np.maximum(0.0, (1 + v) / 2), np.maximum(0.0, (1 - v) / 2)], axis=1)
+        return multinomial_counts(probs, shots, seed, run)[:, 0]
+
+
+class DensityMatrixBackend(AQCBackend):
+    """The exact expectation of what ``QiskitSamplingBackend`` estimates under the same
+    ``execute_kwargs["noise_model"]``, with no shots.
+
+    The program is ``noise.trajectory_program`` of a copy of ``compiler.full_circuit`` with a terminal
+    measure on every qubit, so the errors attached to ``measure`` are in it, as they are in the sampling
+    backend's cost; the compiler's circuit is untouched.  rho is evolved once per program and kept."""
+
+    MAX_QUBITS = MAX_QUBITS
+
+    def __init__(self):
+        self._evolved = _Evolved()
+
+    # checkpoints pickle the whole compiler including its backend
+    def __getstate__(self):
+        return {"_evolved": _Evolved()}
+
+    def _run(self, compiler):
+        from ..noise import trajectory_program
+
+        if getattr(compiler, "soften_global_cost", False):
+            raise NotImplementedError("soften_global_cost is currently only implemented for AerMPSBackend")
+        if getattr(compiler, "general_initial_state", False):
+            raise NotImplementedError("DensityMatrixBackend does not support general_initial_state (its 2 n-qubit "
+                                      "circuit): use QiskitSamplingBackend")
+        n = compiler.full_circuit.num_qubits
+        _refuse_width(n, "DensityMatrixBackend")
+        qc = without_classical_operations(compiler.full_circuit)
+        for q in range(n):
+            qc.measure(q, q)
+        rows, _, _ = trajectory_program(qc, (getattr(compiler, "execute_kwargs", None) or {}).get("noise_model"))
+        return self._evolved.state(n, rows)
+
+    def evaluate_global_cost(self, compiler):
+        """1 - rho_00 / Tr rho: the expectation of the sampling backend's 1 - count("0...0") / shots."""
+        dev = self._run(compiler)
+        return 1 - dev.prob0() / dev.trace()
+
+    def evaluate_local_cost(self, compiler):
+        """The mean over the qubits of P(the qubit reads 1)."""
+        return float(0.5 * (1 - np.mean(self.measure_qubit_expectation_values(compiler))))
+
+    def measure_qubit_expectation_values(self, compiler):
+        dev = self._run(compiler)
+        trace = dev.trace()
+        return [float(z / trace) for z in dev.z_all()]
+
+    def evaluate_circuit(self, compiler):
+        """The outcome probabilities as a dict in the counts key format (all qubits, highest leftmost);
+        outcomes of probability 0 are left out."""
+        dev = self._run(compiler)
+        n = compiler.full_circuit.num_qubits
+        p = dev.probabilities() / dev.trace()
+        return {format(int(k), f"0{n}b"): float(p[k]) for k in np.flatnonzero(p > 0)}
+
+    def pair_rdms(self, compiler, pairs):
+        """The exact 4x4 mixed RDM of every pair (index 2 bit_hi + bit_lo), divided by Tr rho: the ISL
+        sweep's input (``pair_entanglement_measures``)."""
+        dev = self._run(compiler)
+        return dev.pair_rdms(pairs) / dev.trace()

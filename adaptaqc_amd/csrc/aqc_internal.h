@@ -248,6 +248,9 @@ void dev_free(void* p);
 
 // The statevector handle as the samplers (sample.hip) read it (sv.hip).
 int sv_view(aqc_sv_t h, const cplx** state, int* n, hipStream_t* stream);
+// The n-qubit statevector handle for a caller that overwrites every amplitude (dm.hip's diagonal): a
+// deferred reset is dropped, not materialised.  AQC_ERR_ARG, and the handle untouched, for another n.
+int sv_overwrite(aqc_sv_t h, int n, cplx** state, hipStream_t* stream);
 
 // ---- kernel timing (HIP events on the launching stream) ------------------------------
 struct KernelTimer {

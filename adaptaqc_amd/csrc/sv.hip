@@ -921,6 +921,15 @@ int aqc::sv_view(aqc_sv_t h, const cplx** state, int* n, hipStream_t* stream) {
   return AQC_OK;
 }
 
+int aqc::sv_overwrite(aqc_sv_t h, int n, cplx** state, hipStream_t* stream) {
+  AQC_REQUIRE(h->n == n, "the statevector has another qubit count");
+  h->zero_pending = false;  // overwritten
+  h->amp0_ready = false;
+  *state = h->state;
+  *stream = h->stream;
+  return AQC_OK;
+}
+
 static int sv_scratch(aqc_sv_t h, size_t bytes, char** out) {
   if (bytes > h->scratch_cap) {
     AQC_HIP_CHECK(hipStreamSynchronize(h->stream));

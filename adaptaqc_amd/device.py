@@ -97,6 +97,135 @@ class DeviceSV:
         _lib.check(self._l.aqc_sv_set(self.h, _lib.ptr(psi)))
 
 
+class DeviceDM:
+    """The density matrix of n <= 13 qubits resident in HBM (csrc/dm.hip): 4^n complex128, entry (r, c) at
+    r + (c << n).  What Aer's ``method="density_matrix"`` holds: one deterministic evolution of a noisy
+    program gives the exact cost, RDMs, Pauli values and outcome distribution that the trajectory
+    samplers estimate from shots."""
+
+    MAX_QUBITS = 13
+
+    def __init__(self, n):
+        self._l = _lib.lib()
+        self.n = int(n)
+        h = ctypes.c_void_p()
+        _lib.check(self._l.aqc_dm_create(self.n, ctypes.byref(h)))
+        self.h = h
+        self._diag = None  # the diagonal as a DeviceSV, made on first use
+        self._diag_valid = False
+
+    def close(self):
+        if getattr(self, "_diag", None) is not None:
+            self._diag.close()
+            self._diag = None
+        if getattr(self, "h", None) is not None and self.h.value:
+            self._l.aqc_dm_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def reset(self):
+        """rho = |0...0><0...0|."""
+        self._diag_valid = False
+        _lib.check(self._l.aqc_dm_reset(self.h))
+
+    def run(self, rows):
+        """Evolves rho by the program ``rows`` (noise.trajectory_program; aqc_dm_apply): gate rows as
+        U rho U^dag, Kraus rows and groups as sum_k K_k rho K_k^dag.  Returns when it is done."""
+        rows = np.ascontiguousarray(rows, dtype=_lib.OP_DTYPE)
+        self._diag_valid = False
+        _lib.check(self._l.aqc_dm_apply(self.h, _lib.ptr(rows) if len(rows) else None, len(rows)))
+
+    def get(self):
+        """rho as a [2^n, 2^n] complex array (index bit q = qubit q)."""
+        dim = 2 ** self.n
+        out = np.zeros(dim * dim, dtype=np.complex128)
+        _lib.check(self._l.aqc_dm_get(self.h, _lib.ptr(out)))
+        return np.ascontiguousarray(out.reshape(dim, dim).T)  # entry (r, c) at r + (c << n)
+
+    def _trace0(self):
+        out = np.zeros(2)
+        _lib.check(self._l.aqc_dm_trace0(self.h, _lib.dptr(out)))
+        return out
+
+    def prob0(self):
+        """Re rho_00: the probability of reading all zeros (not divided by the trace)."""
+        return float(self._trace0()[0])
+
+    def trace(self):
+        return float(self._trace0()[1])
+
+    def _diagonal(self):
+        """The DeviceSV holding sqrt(rho_kk) (aqc_dm_diag_sv): the statevector readers serve it."""
+        if self._diag is None:
+            self._diag = DeviceSV(self.n)
+        if not self._diag_valid:
+            _lib.check(self._l.aqc_dm_diag_sv(self.h, self._diag.h))
+            self._diag_valid = True
+        return self._diag
+
+    def probabilities(self):
+        """float64 [2^n]: max(0, Re rho_kk)."""
+        return self._diagonal().get().real ** 2
+
+    def sample(self, shots, seed, run=0, u=None):
+        """``shots`` outcomes of all qubits drawn from the diagonal by aqc_sv_sample's rule: uint64[shots]
+        basis indices.  ``u`` as ``DeviceSV.sample``."""
+        return self._diagonal().sample(shots, seed, run, u)
+
+    def z_all(self):
+        """<Z_q> of every qubit from the diagonal (not divided by the trace)."""
+        return self._diagonal().z_all()
+
+    def pauli_expect(self, terms, effects=None):
+        """Re Tr(M_t rho) of every term (aqc_dm_pauli_expect).  ``terms``: qiskit labels (rightmost
+        character = qubit 0) or an (nterms, n) uint8 code array, none all-identity.  ``effects`` None: M_t
+        is the Pauli string; else the [n, 3, 2, 4] POVM effects of noise.readout_effects and M_t the
+        parity operator of the noisy readout of term t."""
+        from . import paulis
+
+        codes = paulis.terms_to_codes(terms, self.n)
+        out = np.zeros(len(codes))
+        if len(codes) == 0:
+            return out
+        eff = None
+        if effects is not None:
+            eff = np.ascontiguousarray(effects, dtype=np.float64)
+            if eff.shape != (self.n, 3, 2, 4):
+                raise ValueError(f"pauli_expect: effects must have shape {(self.n, 3, 2, 4)}")
+        _lib.check(self._l.aqc_dm_pauli_expect(self.h, _lib.ptr(codes), len(codes), _lib.ptr(eff), _lib.ptr(out)))
+        return out
+
+    def pair_rdms(self, pairs):
+        """4x4 reduced density matrices of qubit pairs, conventions of ``DeviceSV.pair_rdms``."""
+        pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1))
+        out = np.zeros(len(pairs) // 2 * 16, dtype=np.complex128)
+        if len(pairs):
+            _lib.check(self._l.aqc_dm_pair_rdms(self.h, _lib.ptr(pairs), len(pairs) // 2, _lib.ptr(out)))
+        return out.reshape(-1, 4, 4)
+
+
+DM_PLAN_COUNTS = ("segments", "steps", "rows", "tile_bits")
+
+
+def dm_plan(n, rows, return_steps=False):
+    """The plan of ``DeviceDM.run`` (aqc_dm_plan; no GPU): a dict of the counts named in DM_PLAN_COUNTS
+    (segments = launches), and with ``return_steps`` also the steps in execution order as a
+    DM_STEP_DTYPE array (kind 0: a unitary step, U in ``m``; kind 1: a superoperator step, S in ``m``;
+    see include/aqc_hip.h)."""
+    rows = np.ascontiguousarray(rows, dtype=_lib.OP_DTYPE)
+    counts = np.zeros(4, dtype=np.int32)
+    prog = _lib.ptr(rows) if len(rows) else None
+    entry = _lib.load().aqc_dm_plan
+    _lib.check(entry(int(n), prog, len(rows), _lib.ptr(counts), None, 0))
+    named = dict(zip(DM_PLAN_COUNTS, (int(c) for c in counts)))
+    if not return_steps:
+        return named
+    steps = np.zeros(int(counts[1]), dtype=_lib.DM_STEP_DTYPE)
+    _lib.check(entry(int(n), prog, len(rows), _lib.ptr(counts), _lib.ptr(steps) if len(steps) else None, len(steps)))
+    return named, steps
+
+
 class DeviceMPS:
     """Vidal-form MPS resident in HBM with Aer MPS-simulator semantics."""
 

@@ -24,6 +24,11 @@ product-unitary error (every operator a scalar times a product of two unitaries:
 ``depolarizing_error(p, 2)``) costs two one-site updates and no SVD; any other is a two-site update whose
 operator is chosen on the device from the pair's reduced density matrix.
 
+The same flat program also runs exactly: up to 13 qubits the density-matrix engine (csrc/dm.hip,
+``device.DeviceDM``, ``backends.DensityMatrixSimulator`` / ``DensityMatrixBackend``) evolves rho by it --
+a gate row as U rho U^dag, a Kraus row or group as sum_k K_k rho K_k^dag -- and reads the cost, the RDMs,
+the Pauli values (with ``readout_effects``) and the outcome distribution off rho with no shot noise.
+
 Out of scope: two errors on one instruction, readout-error matrices, reset, errors on gates of three or
 more qubits.
 """

@@ -386,6 +386,63 @@ int aqc_mps_traj_pauli_counts(int n, int chi_cap, double threshold, int max_chi,
                               uint64_t run, const double* u, int64_t* plus, double* values, double* norms,
                               uint8_t* outcomes);
 
+/* ---- density-matrix engine: replaces Aer's method="density_matrix" under a NoiseModel ---------------
+   rho of n qubits, 1 <= n <= 13, as 4^n interleaved complex128 in device memory: entry (r, c) at index
+   r + (c << n), r and c little-endian in the qubits as the statevector's index (n = 13 is 1 GiB).  One
+   deterministic evolution gives exactly what the trajectory samplers estimate: the noisy cost 1 - rho_00,
+   every pair's RDM, every Pauli term and the outcome distribution.  No atomics, no uniforms: two calls
+   give the same bits.
+   aqc_dm_create: rho = |0...0><0...0|; aqc_dm_reset restores it.  AQC_ERR_ARG for n outside 1 .. 13. */
+typedef struct aqc_dm_s* aqc_dm_t;
+int aqc_dm_create(int n, aqc_dm_t* out);
+int aqc_dm_destroy(aqc_dm_t h);
+int aqc_dm_reset(aqc_dm_t h);
+/* prog: aqc_sv_traj_sample's program, unchanged.  A gate row is rho <- U rho U^dag, an AQC_OP_KRAUS1 row
+   rho <- sum_k K_k rho K_k^dag, an AQC_OP_KRAUS2 group the same sum over its rows (4x4 index 2 b(q1) +
+   b(q0)).  Rows on the same one or two qubits fold into one step, steps into segments of at most 6 qubits,
+   one launch per segment (aqc_dm_plan).  Returns when the evolution is done.
+   AQC_ERR_ARG, before any device call, as aqc_sv_traj_sample: a qubit out of range, a malformed Kraus row
+   or group, sum K^dag K off the identity by more than 1e-9, AQC_OP_MEASURE1 or unknown flags. */
+int aqc_dm_apply(aqc_dm_t h, const aqc_op_t* prog, int nprog);
+/* Host planning of aqc_dm_apply only (no GPU).  counts[0] = segments (= launches), [1] = steps, [2] = the
+   program rows folded into them, [3] = the index bits of the largest tile (at most 12).  steps: NULL, or
+   room for cap steps, filled in execution order.  A step acts on the 4 (nq = 1) or 16 (nq = 2) entries of
+   rho that share every other index bit, at the local index j = r_q0 + 2 c_q0, or (r_q0 + 2 r_q1) +
+   4 (c_q0 + 2 c_q1).  kind 0, unitary: m[0..7] / m[0..31] = U (2x2, or 4x4 with index 2 b(q1) + b(q0)),
+   X <- U X U^dag.  kind 1, superoperator: m[0..31] / m[0..511] = S (4x4 / 16x16, row-major, (re, im)),
+   S[j', j] = sum_k K[r', r] conj(K[c', c]), x <- S x.  Steps of one segment act in the order listed;
+   steps on disjoint qubits may have been reordered against the program.  AQC_ERR_ARG as aqc_dm_apply
+   and for n outside 1 .. 13. */
+typedef struct aqc_dm_step {
+  int32_t kind;
+  int32_t nq;
+  int32_t q0;
+  int32_t q1;
+  int32_t segment;
+  int32_t pad[3];
+  double m[512];
+} aqc_dm_step_t;
+int aqc_dm_plan(int n, const aqc_op_t* prog, int nprog, int* counts, aqc_dm_step_t* steps, int cap);
+/* The host copy of rho: 2 x 4^n doubles. */
+int aqc_dm_get(aqc_dm_t h, double* out);
+/* out[0] = Re rho_00, out[1] = Re Tr rho. */
+int aqc_dm_trace0(aqc_dm_t h, double* out);
+/* Writes a_k = sqrt(max(0, Re rho_kk)) into an n-qubit statevector: aqc_sv_sample then draws shots from
+   the diagonal by its inverse-CDF rule, aqc_sv_z_all gives every <Z>, aqc_sv_get the probabilities'
+   roots.  AQC_ERR_ARG when sv has another qubit count. */
+int aqc_dm_diag_sv(aqc_dm_t h, aqc_sv_t sv);
+/* out[t] = Re Tr(M_t rho).  codes: nterms x n bytes as aqc_sv_traj_pauli_counts (no all-identity term).
+   effects NULL: M_t is the Pauli string.  Otherwise effects is aqc_sv_traj_pair_tomo's [n][3][2][4] table
+   and M_t = (x)_{q in support} (E_q[+] - E_q[-]), folded as aqc_sv_traj_pauli_counts folds it, with any
+   number of general factors (a term reads 2^n 2^ng entries).  Not divided by Tr rho.  One workgroup per
+   term, fixed summation order.  AQC_ERR_ARG: nterms outside 1 .. 65536, a code above 3, an all-identity
+   term, the effects check of aqc_sv_traj_pair_tomo. */
+int aqc_dm_pauli_expect(aqc_dm_t h, const uint8_t* codes, int nterms, const double* effects, double* out);
+/* out[p] = the 4x4 RDM of pair p (16 complex, row-major), conventions of aqc_sv_pair_rdms: index
+   2 bit_hi + bit_lo, hi the pair's larger qubit; the sum over the 2^(n-2) values of the other qubits in a
+   fixed order, one workgroup per pair.  n >= 2, at most 4096 pairs. */
+int aqc_dm_pair_rdms(aqc_dm_t h, const int* pairs, int npairs, double* out);
+
 /* ---- Pauli-string expectation values: replaces circuit_operations_pauli_ops.py:60-100 -------------
    (expectation_value_of_pauli_operator, which runs one rotated circuit per term).
    out[t] = Re <psi| P_t |psi>,  P_t = i^{popcount(x&z)} X^{x} Z^{z}  (a qubit set in both masks is Y);
