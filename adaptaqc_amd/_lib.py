@@ -58,6 +58,7 @@ EXPORTS = (
     "aqc_pair_tomo_probs", "aqc_concurrence_bound_probs", "aqc_multinomial_counts", "aqc_tomo_fit",
     "aqc_dm_create", "aqc_dm_destroy", "aqc_dm_reset", "aqc_dm_apply", "aqc_dm_plan", "aqc_dm_get", "aqc_dm_trace0",
     "aqc_dm_diag_sv", "aqc_dm_pauli_expect", "aqc_dm_pair_rdms",
+    "aqc_dm_apply_adjoint", "aqc_dm_plan_adjoint", "aqc_dm_set", "aqc_dm_set_diag", "aqc_dm_copy", "aqc_dm_transition",
 )
 
 
@@ -195,6 +196,12 @@ _SIGS = {
     "aqc_dm_diag_sv": ([_P, _P], _I),
     "aqc_dm_pauli_expect": ([_P, _P, _I, _P, _P], _I),
     "aqc_dm_pair_rdms": ([_P, _P, _I, _P], _I),
+    "aqc_dm_apply_adjoint": ([_P, _P, _I], _I),
+    "aqc_dm_plan_adjoint": ([_I, _P, _I, _P, _P, _I], _I),
+    "aqc_dm_set": ([_P, _P], _I),
+    "aqc_dm_set_diag": ([_P, _P], _I),
+    "aqc_dm_copy": ([_P, _P], _I),
+    "aqc_dm_transition": ([_P, _P, _I, _P], _I),
 }
 
 

@@ -157,16 +157,44 @@ class DensityMatrixBackend(AQCBackend):
 
     The program is ``noise.trajectory_program`` of a copy of ``compiler.full_circuit`` with a terminal
     measure on every qubit, so the errors attached to ``measure`` are in it, as they are in the sampling
-    backend's cost; the compiler's circuit is untouched.  rho is evolved once per program and kept."""
+    backend's cost; the compiler's circuit is untouched.  rho is evolved once per program and kept.
+
+    ``heisenberg_sweep=True`` (opt-in): Rotosolve / Rotoselect cycles on the global or the local cost read
+    every candidate of a gate off one 4x4 transition matrix between the forward-evolved prefix state and
+    the observable pulled back through the suffix (``cached_rotations.DMHeisenbergSweep``) instead of
+    evolving rho through the whole circuit per candidate; the costs are the same numbers up to rounding.
+    ``checkpoint_bytes`` bounds the device memory of the pulled-back observables kept per cycle (16 x 4^n
+    bytes each, at least one)."""
 
     MAX_QUBITS = MAX_QUBITS
+    # (defaults for a backend restored from a checkpoint written before these existed)
+    heisenberg_sweep = False
+    checkpoint_bytes = 8 << 30
+    _sweep = (0, ())
 
-    def __init__(self):
+    def __init__(self, heisenberg_sweep=False, checkpoint_bytes=8 << 30):
         self._evolved = _Evolved()
+        self.heisenberg_sweep = bool(heisenberg_sweep)
+        self.checkpoint_bytes = int(checkpoint_bytes)
+        self._sweep = (0, [])
 
     # checkpoints pickle the whole compiler including its backend
     def __getstate__(self):
-        return {"_evolved": _Evolved()}
+        return {"_evolved": _Evolved(), "heisenberg_sweep": self.heisenberg_sweep,
+                "checkpoint_bytes": self.checkpoint_bytes, "_sweep": (0, [])}
+
+    def sweep_states(self, n, count):
+        """``count`` device matrices of n qubits for the Heisenberg sweep, kept from cycle to cycle."""
+        from ..device import DeviceDM
+
+        if self._sweep[0] != n:
+            for dev in self._sweep[1]:
+                dev.close()
+            self._sweep = (n, [])
+        states = self._sweep[1]
+        while len(states) < count:
+            states.append(DeviceDM(n))
+        return states[:count]
 
     def _run(self, compiler):
         from ..noise import trajectory_program

@@ -31,6 +31,14 @@
 // readers then serve shots, <Z> and probabilities unchanged), Re Tr(M rho) of Pauli terms or of the
 // parity operators of a noisy readout (traj.hip's folding into an x mask, a z mask, a scalar and general
 // factors, here any number of them: a term reads 2^n 2^ng entries), and the pairs' 4x4 RDMs.
+//
+// Heisenberg picture (cached_rotations.DMHeisenbergSweep).  aqc_dm_apply_adjoint is X <- Lambda^dag(X): the
+// forward plan backwards (segments and the steps inside them in reverse order, U^H for U, S^H for S) through
+// the same k_dm_segment; aqc_dm_set, aqc_dm_set_diag and aqc_dm_copy load an observable and checkpoint it.
+// k_dm_transition reads two matrices once each into T[j', j] = sum_o conj(A[j', o]) B[j, o] at one qubit's
+// local index j = r_q + 2 c_q: Tr(A^H (S_q (x) id)(B)) = sum S[j', j] T[j', j] for any one-qubit
+// superoperator S, so every candidate gate at a position, with its error, costs 16 host MACs.  It is the one
+// reader spread over workgroups (a partial per workgroup, a second launch adds them in order).
 #include <algorithm>
 #include <cmath>
 #include <complex>
@@ -209,6 +217,65 @@ __global__ __launch_bounds__(kThreads) void k_dm_segment(cplx* __restrict__ rho,
 __global__ void k_dm_reset(cplx* __restrict__ rho, size_t total) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   for (; i < total; i += (size_t)gridDim.x * blockDim.x) rho[i] = aqc::cmk(i == 0 ? 1.0 : 0.0, 0.0);
+}
+
+// rho = diag(d): the observable of a cost that is linear in the outcome distribution
+__global__ void k_dm_set_diag(cplx* __restrict__ rho, int n, const double* __restrict__ d, size_t total) {
+  const size_t mask = ((size_t)1 << n) - 1;
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t r = i & mask;
+    rho[i] = aqc::cmk((i >> n) == r ? d[r] : 0.0, 0.0);
+  }
+}
+
+// part[block][j' * 4 + j] = sum over the block's o of conj(A[j', o]) B[j, o]: j = r_q + 2 c_q the local
+// index of qubit q, o the other 2n - 2 index bits.  Lanes take consecutive o, so a wave's loads are
+// contiguous up to the one split that bit q makes in a lane run; a thread's terms add in index order,
+// then the wave butterfly and the waves in order (1 or 4 of them).  k_dm_transition_sum adds the blocks
+// in order.
+__global__ __launch_bounds__(kThreads) void k_dm_transition(const cplx* __restrict__ A, const cplx* __restrict__ B,
+                                                            int n, int q, double* __restrict__ part) {
+  __shared__ double red[kThreads / 64][32];
+  const uint32_t total = 1u << (2 * n - 2);
+  double acc[32];
+#pragma unroll
+  for (int e = 0; e < 32; ++e) acc[e] = 0.0;
+  for (uint32_t o = blockIdx.x * blockDim.x + threadIdx.x; o < total; o += gridDim.x * blockDim.x) {
+    const size_t base = insert_zero(insert_zero(o, q), n + q);
+    cplx a[4], b[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const size_t at = base | ((size_t)(j & 1) << q) | ((size_t)(j >> 1) << (n + q));
+      a[j] = A[at];
+      b[j] = B[at];
+    }
+#pragma unroll
+    for (int jp = 0; jp < 4; ++jp)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {  // conj(a) b
+        acc[2 * (4 * jp + j)] += a[jp].x * b[j].x + a[jp].y * b[j].y;
+        acc[2 * (4 * jp + j) + 1] += a[jp].x * b[j].y - a[jp].y * b[j].x;
+      }
+  }
+#pragma unroll
+  for (int e = 0; e < 32; ++e) acc[e] = wave_sum(acc[e]);
+  if ((threadIdx.x & 63) == 0)
+#pragma unroll
+    for (int e = 0; e < 32; ++e) red[threadIdx.x >> 6][e] = acc[e];
+  __syncthreads();
+  if (threadIdx.x < 32) {
+    double s = 0.0;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s += red[w][threadIdx.x];
+    part[(size_t)blockIdx.x * 32 + threadIdx.x] = s;
+  }
+}
+
+// out[e] = sum_b part[b][e], b ascending (one workgroup of 32 threads)
+__global__ void k_dm_transition_sum(const double* __restrict__ part, int nblocks, double* __restrict__ out) {
+  double s = 0.0;
+  for (int b = 0; b < nblocks; ++b) s += part[(size_t)b * 32 + threadIdx.x];
+  out[threadIdx.x] = s;
 }
 
 // out[0] = Re rho_00, out[1] = Re Tr rho (one workgroup)
@@ -503,7 +570,17 @@ void push_record(std::vector<double>& words, int kind, int t0, int t1, const hma
   }
 }
 
-int build_plan(int n, const aqc_op_t* prog, int nprog, Plan& plan) {
+hmat dagger(const hmat& m, int d) {
+  hmat o((size_t)d * d);
+  for (int i = 0; i < d; ++i)
+    for (int j = 0; j < d; ++j) o[(size_t)i * d + j] = std::conj(m[(size_t)j * d + i]);
+  return o;
+}
+
+// adjoint: the plan of the adjoint map X <- Lambda^dag(X).  The forward plan's segments in reverse order,
+// each segment's steps in reverse order, every U replaced by U^H and every S by S^H (the adjoint of x <- S x
+// under Tr(A^H B) in the same local index); tiles and records are the forward plan's.
+int build_plan(int n, const aqc_op_t* prog, int nprog, Plan& plan, bool adjoint = false) {
   std::vector<Event> evs;
   if (int rc = parse_events(n, prog, nprog, evs)) return rc;
   // ---- steps ----
@@ -541,12 +618,12 @@ int build_plan(int n, const aqc_op_t* prog, int nprog, Plan& plan) {
   plan.kq = kq;
   const int ns = (int)live.size();
   std::vector<char> done(ns, 0);
-  std::vector<int> order;
+  std::vector<uint32_t> seg_mask;
+  std::vector<std::vector<int>> seg_steps;
   int remaining = ns, first = 0;
   while (remaining > 0) {
     while (first < ns && done[first]) ++first;
     uint32_t qmask = 0, blocked = 0;
-    const int seg = (int)plan.segs.size();
     std::vector<int> mine;
     for (int i = first; i < ns; ++i) {
       if (done[i]) continue;
@@ -563,18 +640,33 @@ int build_plan(int n, const aqc_op_t* prog, int nprog, Plan& plan) {
       if (__builtin_popcount(blocked) >= n) break;
     }
     for (int b = 0; b < n && __builtin_popcount(qmask) < kq; ++b) qmask |= 1u << b;  // the lowest free qubits
+    seg_mask.push_back(qmask);
+    seg_steps.push_back(std::move(mine));
+  }
+  if (adjoint) {
+    std::reverse(seg_mask.begin(), seg_mask.end());
+    std::reverse(seg_steps.begin(), seg_steps.end());
+    for (std::vector<int>& mine : seg_steps) std::reverse(mine.begin(), mine.end());
+    for (HStep& st : live) {
+      const int d = 1 << st.nq;
+      if (st.unitary) st.U = dagger(st.U, d);
+      else st.S = dagger(st.S, d * d);
+    }
+  }
+  std::vector<int> order;
+  for (size_t seg = 0; seg < seg_steps.size(); ++seg) {
     DmSegArg sa;
     std::memset(&sa, 0, sizeof(sa));
     int local_of[32], cnt = 0;
     for (int b = 0; b < n; ++b)
-      if ((qmask >> b) & 1u) {
+      if ((seg_mask[seg] >> b) & 1u) {
         sa.tq[cnt] = b;
         local_of[b] = cnt++;
       }
     sa.word_off = (int)(plan.words.size() / 2);
-    for (int i : mine) {
+    for (int i : seg_steps[seg]) {
       HStep& st = live[i];
-      st.seg = seg;
+      st.seg = (int)seg;
       if (st.nq == 1) push_record(plan.words, kRecS1, local_of[st.q0], 0, st.unitary ? lift(st.U, 2) : st.S, 16);
       else if (st.unitary) push_record(plan.words, kRecU2, local_of[st.q0], local_of[st.q1], st.U, 16);
       else push_record(plan.words, kRecS2, local_of[st.q0], local_of[st.q1], st.S, 256);
@@ -715,12 +807,13 @@ int aqc_dm_reset(aqc_dm_t h) {
   return AQC_OK;
 }
 
-int aqc_dm_plan(int n, const aqc_op_t* prog, int nprog, int* counts, aqc_dm_step_t* steps, int cap) {
-  t_entry = "aqc_dm_plan";
-  AQC_REQUIRE(counts && nprog >= 0 && (prog || nprog == 0) && (steps || cap == 0) && cap >= 0, "aqc_dm_plan: bad arguments");
-  AQC_REQUIRE(n >= 1 && n <= kMaxQubits, "aqc_dm_plan: n must be in 1 .. 13");
+static int plan_out(const char* entry, bool adjoint, int n, const aqc_op_t* prog, int nprog, int* counts,
+                    aqc_dm_step_t* steps, int cap) {
+  t_entry = entry;
+  if (!(counts && nprog >= 0 && (prog || nprog == 0) && (steps || cap == 0) && cap >= 0)) return fail("bad arguments");
+  if (!(n >= 1 && n <= kMaxQubits)) return fail("n must be in 1 .. 13");
   Plan plan;
-  if (int rc = build_plan(n, prog, nprog, plan)) return rc;
+  if (int rc = build_plan(n, prog, nprog, plan, adjoint)) return rc;
   counts[0] = (int)plan.segs.size();
   counts[1] = (int)plan.steps.size();
   counts[2] = nprog;
@@ -740,11 +833,17 @@ int aqc_dm_plan(int n, const aqc_op_t* prog, int nprog, int* counts, aqc_dm_step
   return AQC_OK;
 }
 
-int aqc_dm_apply(aqc_dm_t h, const aqc_op_t* prog, int nprog) {
-  t_entry = "aqc_dm_apply";
-  AQC_REQUIRE(h && nprog >= 0 && (prog || nprog == 0), "aqc_dm_apply: null argument");
+int aqc_dm_plan(int n, const aqc_op_t* prog, int nprog, int* counts, aqc_dm_step_t* steps, int cap) {
+  return plan_out("aqc_dm_plan", false, n, prog, nprog, counts, steps, cap);
+}
+
+int aqc_dm_plan_adjoint(int n, const aqc_op_t* prog, int nprog, int* counts, aqc_dm_step_t* steps, int cap) {
+  return plan_out("aqc_dm_plan_adjoint", true, n, prog, nprog, counts, steps, cap);
+}
+
+static int run_program(aqc_dm_t h, const aqc_op_t* prog, int nprog, bool adjoint) {
   Plan plan;
-  if (int rc = build_plan(h->n, prog, nprog, plan)) return rc;
+  if (int rc = build_plan(h->n, prog, nprog, plan, adjoint)) return rc;
   if (plan.segs.empty()) return AQC_OK;
   char* buf = nullptr;
   const size_t wb = plan.words.size() * sizeof(double);
@@ -766,6 +865,73 @@ int aqc_dm_apply(aqc_dm_t h, const aqc_op_t* prog, int nprog) {
   }
   // (the plan's host copy goes out of scope here, and a fault belongs to this call)
   AQC_HIP_CHECK(hipStreamSynchronize(h->stream));
+  return AQC_OK;
+}
+
+int aqc_dm_apply(aqc_dm_t h, const aqc_op_t* prog, int nprog) {
+  t_entry = "aqc_dm_apply";
+  AQC_REQUIRE(h && nprog >= 0 && (prog || nprog == 0), "aqc_dm_apply: null argument");
+  return run_program(h, prog, nprog, false);
+}
+
+int aqc_dm_apply_adjoint(aqc_dm_t h, const aqc_op_t* prog, int nprog) {
+  t_entry = "aqc_dm_apply_adjoint";
+  AQC_REQUIRE(h && nprog >= 0 && (prog || nprog == 0), "aqc_dm_apply_adjoint: null argument");
+  return run_program(h, prog, nprog, true);
+}
+
+int aqc_dm_copy(aqc_dm_t dst, aqc_dm_t src) {
+  AQC_REQUIRE(dst && src, "aqc_dm_copy: null handle");
+  AQC_REQUIRE(dst->n == src->n, "aqc_dm_copy: the two matrices have different qubit counts");
+  if (dst == src) return AQC_OK;
+  AQC_HIP_CHECK(hipMemcpyAsync(dst->rho, src->rho, sizeof(cplx) << (2 * dst->n), hipMemcpyDeviceToDevice, dst->stream));
+  AQC_HIP_CHECK(hipStreamSynchronize(dst->stream));
+  return AQC_OK;
+}
+
+int aqc_dm_set(aqc_dm_t h, const double* in) {
+  AQC_REQUIRE(h && in, "aqc_dm_set: null argument");
+  AQC_HIP_CHECK(hipMemcpyAsync(h->rho, in, sizeof(cplx) << (2 * h->n), hipMemcpyHostToDevice, h->stream));
+  AQC_HIP_CHECK(hipStreamSynchronize(h->stream));
+  return AQC_OK;
+}
+
+int aqc_dm_set_diag(aqc_dm_t h, const double* d) {
+  AQC_REQUIRE(h && d, "aqc_dm_set_diag: null argument");
+  const size_t db = sizeof(double) << h->n;
+  char* buf = nullptr;
+  if (int rc = dm_buf(h, db, &buf)) return rc;
+  AQC_HIP_CHECK(hipMemcpyAsync(buf, d, db, hipMemcpyHostToDevice, h->stream));
+  const size_t total = (size_t)1 << (2 * h->n);
+  const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, 65536);
+  hipLaunchKernelGGL(k_dm_set_diag, dim3(grid), dim3(256), 0, h->stream, h->rho, h->n, (const double*)buf, total);
+  AQC_CHECK_LAUNCH();
+  AQC_HIP_CHECK(hipStreamSynchronize(h->stream));  // (d is read by the copy until here)
+  return AQC_OK;
+}
+
+int aqc_dm_transition(aqc_dm_t a, aqc_dm_t b, int q, double* out) {
+  AQC_REQUIRE(a && b && out, "aqc_dm_transition: null argument");
+  AQC_REQUIRE(a->n == b->n, "aqc_dm_transition: the two matrices have different qubit counts");
+  AQC_REQUIRE(q >= 0 && q < a->n, "aqc_dm_transition: qubit out of range");
+  const int n = a->n;
+  // one workgroup while a thread has at most one o (4^(n-1) <= 256); else one o per thread, in one-wave
+  // workgroups until 256-thread ones cover the 256 CUs (n = 8: 256 waves), and at most 1024 workgroups
+  const size_t total = (size_t)1 << (2 * n - 2);
+  const int threads = total <= (size_t)kThreads || total / kThreads >= 256 ? kThreads : 64;
+  const int nblocks = total <= (size_t)kThreads ? 1 : (int)std::min<size_t>(total / threads, 1024);
+  const size_t pb = aqc::up256((size_t)nblocks * 32 * sizeof(double));
+  char* buf = nullptr;
+  if (int rc = dm_buf(a, pb + 32 * sizeof(double), &buf)) return rc;
+  aqc::KernelTimer::begin(a->stream, "dm_transition", 32.0 * std::ldexp(1.0, 2 * n), 0.0);
+  hipLaunchKernelGGL(k_dm_transition, dim3(nblocks), dim3(threads), 0, a->stream, a->rho, b->rho, n, q, (double*)buf);
+  aqc::KernelTimer::end(a->stream);
+  AQC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_dm_transition_sum, dim3(1), dim3(32), 0, a->stream, (const double*)buf, nblocks,
+                     (double*)(buf + pb));
+  AQC_CHECK_LAUNCH();
+  AQC_HIP_CHECK(hipMemcpyAsync(out, buf + pb, 32 * sizeof(double), hipMemcpyDeviceToHost, a->stream));
+  AQC_HIP_CHECK(hipStreamSynchronize(a->stream));
   return AQC_OK;
 }
 

@@ -136,12 +136,59 @@ class DeviceDM:
         self._diag_valid = False
         _lib.check(self._l.aqc_dm_apply(self.h, _lib.ptr(rows) if len(rows) else None, len(rows)))
 
+    def run_adjoint(self, rows):
+        """X <- Lambda^dag(X) for the map Lambda of ``run(rows)`` (aqc_dm_apply_adjoint): the program in
+        reverse, gate rows as U^dag X U, Kraus rows and groups as sum_k K_k^dag X K_k -- an observable
+        pushed backwards through the program.  Tr(X^H Lambda(rho)) = Tr(Lambda^dag(X)^H rho)."""
+        rows = np.ascontiguousarray(rows, dtype=_lib.OP_DTYPE)
+        self._diag_valid = False
+        _lib.check(self._l.aqc_dm_apply_adjoint(self.h, _lib.ptr(rows) if len(rows) else None, len(rows)))
+
     def get(self):
         """rho as a [2^n, 2^n] complex array (index bit q = qubit q)."""
         dim = 2 ** self.n
         out = np.zeros(dim * dim, dtype=np.complex128)
         _lib.check(self._l.aqc_dm_get(self.h, _lib.ptr(out)))
         return np.ascontiguousarray(out.reshape(dim, dim).T)  # entry (r, c) at r + (c << n)
+
+    def set(self, x):
+        """Uploads a [2^n, 2^n] complex array with ``get``'s convention: any matrix, Hermitian or not."""
+        dim = 2 ** self.n
+        x = np.asarray(x, dtype=np.complex128)
+        if x.shape != (dim, dim):
+            raise ValueError(f"set: the matrix must have shape {(dim, dim)}")
+        flat = np.ascontiguousarray(x.T).reshape(-1)
+        self._diag_valid = False
+        _lib.check(self._l.aqc_dm_set(self.h, _lib.ptr(flat)))
+
+    def set_diag(self, d):
+        """The matrix diag(d) from 2^n real entries (aqc_dm_set_diag)."""
+        d = np.ascontiguousarray(d, dtype=np.float64).reshape(-1)
+        if len(d) != 2 ** self.n:
+            raise ValueError(f"set_diag: {2 ** self.n} diagonal entries expected")
+        self._diag_valid = False
+        _lib.check(self._l.aqc_dm_set_diag(self.h, _lib.dptr(d)))
+
+    def copy_from(self, other):
+        """self <- other on the device (aqc_dm_copy; the same qubit count)."""
+        self._diag_valid = False
+        _lib.check(self._l.aqc_dm_copy(self.h, other.h))
+
+    def transition(self, ket, q):
+        """The [4, 4] complex T[j', j] = sum_o conj(self[j', o]) ket[j, o] (aqc_dm_transition): j = r_q +
+        2 c_q the local index of qubit ``q``, o every other index bit.  For a superoperator S on qubit q
+        (``noise.candidate_superoperator``), Tr(self^H (S_q (x) id)(ket)) = sum(S * T): with self an
+        observable pulled back through the gates after a one-qubit gate and ``ket`` the state before it,
+        one scan of both prices every candidate for that gate.  Fixed summation order."""
+        out = np.zeros(16, dtype=np.complex128)
+        _lib.check(self._l.aqc_dm_transition(self.h, ket.h, int(q), _lib.ptr(out)))
+        return out.reshape(4, 4)
+
+    def inner(self, other):
+        """Tr(self^H other), the Hilbert-Schmidt inner product (the trace of ``transition(other, 0)``).
+        For density matrices ``rho.inner(rho)`` is the purity Tr rho^2 and ``rho.inner(sigma)`` the state
+        overlap Tr(rho sigma) (real up to rounding)."""
+        return complex(np.trace(self.transition(other, 0)))
 
     def _trace0(self):
         out = np.zeros(2)
@@ -208,15 +255,15 @@ class DeviceDM:
 DM_PLAN_COUNTS = ("segments", "steps", "rows", "tile_bits")
 
 
-def dm_plan(n, rows, return_steps=False):
+def dm_plan(n, rows, return_steps=False, adjoint=False):
     """The plan of ``DeviceDM.run`` (aqc_dm_plan; no GPU): a dict of the counts named in DM_PLAN_COUNTS
     (segments = launches), and with ``return_steps`` also the steps in execution order as a
     DM_STEP_DTYPE array (kind 0: a unitary step, U in ``m``; kind 1: a superoperator step, S in ``m``;
-    see include/aqc_hip.h)."""
+    see include/aqc_hip.h).  ``adjoint``: the plan of ``DeviceDM.run_adjoint`` (aqc_dm_plan_adjoint)."""
     rows = np.ascontiguousarray(rows, dtype=_lib.OP_DTYPE)
     counts = np.zeros(4, dtype=np.int32)
     prog = _lib.ptr(rows) if len(rows) else None
-    entry = _lib.load().aqc_dm_plan
+    entry = _lib.load().aqc_dm_plan_adjoint if adjoint else _lib.load().aqc_dm_plan
     _lib.check(entry(int(n), prog, len(rows), _lib.ptr(counts), None, 0))
     named = dict(zip(DM_PLAN_COUNTS, (int(c) for c in counts)))
     if not return_steps:

@@ -354,6 +354,19 @@ def readout_effects(n, noise_model):
     return out
 
 
+def candidate_superoperator(matrix, name, qubit, noise_model):
+    """The 4x4 superoperator S of the one-qubit gate ``matrix`` followed by the channels that
+    ``noise_model`` attaches to instruction ``name`` on ``(qubit,)``: S[r' + 2 c', r + 2 c] =
+    sum_k (K_k V)[r', r] conj((K_k V)[c', c]), the local index of the density-matrix engine's steps
+    (``DeviceDM.transition``).  ``noise_model`` None, or a noiseless instruction: the lifted gate."""
+    v = np.asarray(matrix, dtype=complex).reshape(2, 2)
+    s = np.kron(v.conj(), v)
+    if noise_model is not None:
+        for _, error in noise_model.channels(name, (int(qubit),)):
+            s = sum(np.kron(k.conj(), k) for k in error.kraus) @ s
+    return s
+
+
 def trajectory_program(circuit, noise_model):
     """(rows, n_events, measured): the flat program of aqc_sv_traj_sample for ``circuit`` under
     ``noise_model``.  Each gate of ``device_ops(circuit)`` is a gate row; after a gate that carries an

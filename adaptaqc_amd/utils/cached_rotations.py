@@ -38,6 +38,12 @@ candidates differ in one single-qubit gate, so:
 * Statevector, local cost (aer_sv_backend.py:32-35, 49-59): no transition shortcut (every <Z_i> of
   every candidate); the prefix state is cached and the candidates replay the suffix from it.
   The softened cost raises on the statevector backend, as in the reference (generic path).
+* Density matrix under a noise model, global or local cost (``DensityMatrixBackend(heisenberg_sweep=
+  True)``): both costs are linear in the final rho, so the statevector trick carries over with the
+  observable pulled back through the suffix in the Heisenberg picture (aqc_dm_apply_adjoint), rho pushed
+  forward through the prefix, and a 4x4 transition matrix (aqc_dm_transition) contracted with each
+  candidate's superoperator, its error included.  Noise makes the suffix non-invertible, so the
+  pulled-back observable is checkpointed per cycle instead of advanced (``DMHeisenbergSweep``).
 
 The compiler's ``cost_evaluation_counter`` advances by the number of evaluations the reference
 would have made, so histories and logs stay comparable.
@@ -303,12 +309,143 @@ class SVPrefixBatch(_SweepBase):
         return [float(0.5 * (1 - np.mean(st.z_all()))) for st in self.cand[:len(mats)]]
 
 
+class DMHeisenbergSweep(_SweepBase):
+    """Density matrix, global or local cost under a noise model: every candidate of a gate from one 4x4
+    transition matrix.
+
+    Both costs are linear in the final rho: Tr(O rho_final) / Tr rho with O = |0...0><0...0| (global:
+    1 minus it) or O = diag(popcount(k) / n) (local).  With rho_P the state after the gates before the
+    varied one (errors included) and M = Lambda_S^dag(O) the observable pulled back through everything
+    after it (the errors on the terminal measures included), a candidate V followed by its own error is a
+    4x4 superoperator S on the gate's qubit and its cost is sum(S * T) with T = M.transition(rho_P, q).
+
+    Noise makes Lambda_S non-invertible, so M is not advanced gate by gate as ``SVTransitionSweep``
+    advances chi; it is checkpointed.  A cycle visits its gates in ascending order, and M at a position
+    depends only on later gates, which the cycle has not touched yet: ``prepare`` walks backwards from
+    the end once and keeps M at every position of the cycle (at most ``capacity`` matrices at a time:
+    the lowest positions first, and another backward pass for the next ones when they run out).
+    ``costs`` needs the gate name of every candidate (``takes_names``): the error after a gate is
+    looked up by name."""
+
+    takes_names = True
+
+    def __init__(self, compiler, kind="global", max_checkpoints=None):
+        super().__init__(compiler)
+        if kind not in ("global", "local"):
+            raise ValueError("DMHeisenbergSweep: the global or the local cost")
+        self.kind = kind
+        self.n = n = compiler.full_circuit.num_qubits
+        self.noise_model = (getattr(compiler, "execute_kwargs", None) or {}).get("noise_model")
+        budget = int(getattr(compiler.backend, "checkpoint_bytes", 8 << 30))
+        self.capacity = max(1, int(max_checkpoints) if max_checkpoints is not None else budget // (16 * 4 ** n))
+        self._pool = getattr(compiler.backend, "sweep_states", None)
+        self._own = []
+        self.rho, self.obs = self._states(2)
+        self.cycle = []    # the positions of the current cycle, ascending
+        self.where = {}    # position -> the checkpoint that holds its M
+        self.trace = 1.0
+        self.backward_passes = 0
+
+    def _states(self, count):
+        """The first ``count`` device matrices: rho_P, the backward pass's M, then the checkpoints (the
+        backend's, which outlive this evaluator: a compile makes one evaluator per cycle)."""
+        from ..device import DeviceDM
+
+        if self._pool is not None:
+            return self._pool(self.n, count)
+        while len(self._own) < count:
+            self._own.append(DeviceDM(self.n))
+        return self._own[:count]
+
+    def _rows(self, lo, hi, measures=False):
+        """The program of ``data[lo:hi]`` under the noise model; with ``measures`` (the piece a backward
+        pass starts with) followed by the errors of one terminal measure per qubit, as the backend's
+        program ends."""
+        from ..noise import kraus_row, trajectory_program
+
+        circ = self.compiler.full_circuit
+        view = _View(circ, lo, hi)
+        view.data = [ins for ins in view.data if ins.operation.name != "measure"]
+        rows = trajectory_program(view, self.noise_model)[0]
+        if measures and self.noise_model is not None:
+            tail = [kraus_row(e, q) for k in range(self.n) for q, e in self.noise_model.channels("measure", (k,))]
+            if tail:
+                rows = np.concatenate([rows] + tail)
+        return rows
+
+    def _checkpoint(self, first):
+        """One backward pass: M at cycle[first], ... for as many positions as there are checkpoints."""
+        positions = self.cycle[first:first + self.capacity]
+        slots = self._states(2 + len(positions))[2:]
+        if self.kind == "global":
+            self.obs.reset()
+        else:
+            k = np.arange(2 ** self.n, dtype=np.uint64)
+            pop = sum(((k >> np.uint64(b)) & np.uint64(1)).astype(np.float64) for b in range(self.n))
+            self.obs.set_diag(pop / self.n)
+        self.where = {}
+        hi, measures = len(self.compiler.full_circuit.data), True
+        for slot, p in zip(reversed(slots), reversed(positions)):
+            self.obs.run_adjoint(self._rows(p + 1, hi, measures))
+            slot.copy_from(self.obs)
+            self.where[p] = slot
+            hi, measures = p + 1, False
+        self.backward_passes += 1
+
+    def prepare(self, indices):
+        """``indices``: the positions the cycle will visit, in ascending order."""
+        self.cycle = sorted(int(i) for i in indices)
+        self.pos = None
+        self.where = {}
+        if self.cycle:
+            self._checkpoint(0)
+
+    def goto(self, index):
+        index = int(index)
+        if self.pos is None or index < self.pos:
+            if self.pos is not None or index not in self.cycle:
+                # a step back (the gates behind it have changed since the pass), or no prepare: M anew
+                self.cycle = [index] + [p for p in self.cycle if p > index]
+                self.where = {}
+            self.rho.reset()
+            self.rho.run(self._rows(0, index))
+        elif index > self.pos:
+            self.rho.run(self._rows(self.pos, index))  # with the gate just replaced and its error
+        self.pos = index
+        if index not in self.where:
+            if index not in self.cycle:
+                self.cycle = sorted(set(self.cycle) | {index})
+            self._checkpoint(self.cycle.index(index))  # the gates behind index are still unchanged
+        self.trace = self.rho.trace()
+
+    def costs(self, index, mats, names=None):
+        from ..noise import candidate_superoperator
+
+        if names is None:
+            if self.noise_model is not None:
+                raise ValueError("DMHeisenbergSweep.costs: the candidates' gate names select their errors")
+            names = [None] * len(mats)
+        q = _ops_qubit(self.compiler.full_circuit, index)
+        t = self.where[index].transition(self.rho, q)
+        vals = [float(np.sum(candidate_superoperator(m, name, q, self.noise_model) * t).real / self.trace)
+                for m, name in zip(mats, names)]
+        return [1.0 - v for v in vals] if self.kind == "global" else vals
+
+
 def make_evaluator(compiler):
     """The cached evaluator for the compiler's current settings, or None (generic path)."""
     from ..backends.aer_mps_backend import AerMPSBackend
     from ..backends.aer_sv_backend import AerSVBackend
+    from ..backends.density_matrix_backend import DensityMatrixBackend
 
     kind = _cost_kind(compiler)
+    if isinstance(compiler.backend, DensityMatrixBackend):
+        # opt-in; general_initial_state and a circuit too wide keep the backend's refusals (generic path)
+        if (compiler.backend.heisenberg_sweep and kind in ("global", "local")
+                and not getattr(compiler, "general_initial_state", False)
+                and compiler.full_circuit.num_qubits <= DensityMatrixBackend.MAX_QUBITS):
+            return DMHeisenbergSweep(compiler, kind)
+        return None
     if isinstance(compiler.backend, AerMPSBackend):
         return MPSPrefixBatch(compiler, kind)
     if isinstance(compiler.backend, AerSVBackend):

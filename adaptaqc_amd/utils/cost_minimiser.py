@@ -112,10 +112,15 @@ class CostMinimiser:
     def _reduce_cost_cached(self, ev, change_1q_gate_kind, sample):
         """_reduce_cost with every candidate of a gate from one cached evaluation: the same
         candidates, sinusoid fits and selection rules as replace_with_best_1q_gate /
-        find_best_angle, in the same gate order."""
+        find_best_angle, in the same gate order.  An evaluator with ``prepare`` is told the cycle's
+        positions first; one with ``takes_names`` also gets every candidate's gate name (under a noise
+        model the error after a candidate depends on it; the Rotoselect identity candidate is rx)."""
         from .cached_rotations import rotation
 
         cost = 1
+        takes_names = getattr(ev, "takes_names", False)
+        if hasattr(ev, "prepare"):
+            ev.prepare([i for i in sample if co.is_supported_1q_gate(self.full_circuit.data[i].operation)])
         for index in sample:
             old_gate = self.full_circuit.data[index].operation
             if not co.is_supported_1q_gate(old_gate):
@@ -123,10 +128,11 @@ class CostMinimiser:
             ev.goto(index)
             if change_1q_gate_kind:
                 names = co.SUPPORTED_1Q_GATES
-                mats = [rotation("rx", 0.0)]
+                mats, cand = [rotation("rx", 0.0)], ["rx"]
                 for name in names:
                     mats += [rotation(name, np.pi / 2), rotation(name, -np.pi / 2)]
-                c = ev.costs(index, mats)
+                    cand += [name, name]
+                c = ev.costs(index, mats, names=cand) if takes_names else ev.costs(index, mats)
                 ev.count(1 + 2 * len(names))
                 co.replace_1q_gate(self.full_circuit, index, "rx", 0)
                 best_name, best_angle, best_cost = None, None, 1
@@ -138,7 +144,8 @@ class CostMinimiser:
                 cost = best_cost
             else:
                 name = old_gate.label
-                c = ev.costs(index, [rotation(name, 0.0), rotation(name, np.pi / 2), rotation(name, -np.pi / 2)])
+                mats = [rotation(name, 0.0), rotation(name, np.pi / 2), rotation(name, -np.pi / 2)]
+                c = ev.costs(index, mats, names=[name] * 3) if takes_names else ev.costs(index, mats)
                 ev.count(3)
                 angle, cost = minimum_of_sinusoidal(c[0], c[1], c[2])
                 co.replace_1q_gate(self.full_circuit, index, name, angle)

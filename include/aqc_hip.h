@@ -423,8 +423,34 @@ typedef struct aqc_dm_step {
   double m[512];
 } aqc_dm_step_t;
 int aqc_dm_plan(int n, const aqc_op_t* prog, int nprog, int* counts, aqc_dm_step_t* steps, int cap);
+/* X <- Lambda^dag(X), Lambda the map of aqc_dm_apply for the same rows (the Heisenberg picture): the
+   whole program in reverse, a gate row as X <- U^dag X U, a Kraus row or group as X <- sum_k K_k^dag X K_k.
+   The forward plan run backwards: its segments in reverse order, each segment's steps in reverse order,
+   every U replaced by U^H and every S by S^H (the adjoint of x <- S x under Tr(A^H B), in the same local
+   index); the tiles, records and kernel are aqc_dm_apply's.  Tr(X^H Lambda(rho)) = Tr(Lambda^dag(X)^H rho).
+   X is any complex matrix (aqc_dm_set).  Argument checks as aqc_dm_apply. */
+int aqc_dm_apply_adjoint(aqc_dm_t h, const aqc_op_t* prog, int nprog);
+/* aqc_dm_plan for aqc_dm_apply_adjoint: the steps in the order it executes them, with the matrices it
+   uses.  The counts equal the forward plan's. */
+int aqc_dm_plan_adjoint(int n, const aqc_op_t* prog, int nprog, int* counts, aqc_dm_step_t* steps, int cap);
 /* The host copy of rho: 2 x 4^n doubles. */
 int aqc_dm_get(aqc_dm_t h, double* out);
+/* Uploads 2 x 4^n doubles in aqc_dm_get's layout: any complex matrix, Hermitian or not. */
+int aqc_dm_set(aqc_dm_t h, const double* in);
+/* The matrix diag(d): zero everywhere but the 2^n real diagonal entries d[k] (an observable that is
+   diagonal in the computational basis, for aqc_dm_apply_adjoint). */
+int aqc_dm_set_diag(aqc_dm_t h, const double* d);
+/* dst <- src on the device.  AQC_ERR_ARG when the qubit counts differ. */
+int aqc_dm_copy(aqc_dm_t dst, aqc_dm_t src);
+/* out = T, 4x4 complex, row-major as (re, im): T[j', j] = sum_o conj(A[j', o]) B[j, o], with j = r_q + 2 c_q
+   the local index of qubit q (bit q and bit n + q of the entry index) and o the other 2n - 2 index bits.
+   For any superoperator S on qubit q, Tr(A^H (S_q (x) id)(B)) = sum_{j', j} S[j', j] T[j', j]: with
+   A = Lambda_S^dag(O) and B the state before a one-qubit gate, every candidate gate's cost from one scan.
+   sum_j T[j, j] = Tr(A^H B).  A and B are read once each; the scan is spread over workgroups (one when
+   4^(n-1) <= 256), each writing a partial in a fixed order, and a second pass adds the partials in order:
+   no atomics, two calls give the same bits.  a == b is allowed.  AQC_ERR_ARG: q outside 0 .. n-1, different
+   qubit counts. */
+int aqc_dm_transition(aqc_dm_t a, aqc_dm_t b, int q, double* out);
 /* out[0] = Re rho_00, out[1] = Re Tr rho. */
 int aqc_dm_trace0(aqc_dm_t h, double* out);
 /* Writes a_k = sqrt(max(0, Re rho_kk)) into an n-qubit statevector: aqc_sv_sample then draws shots from
