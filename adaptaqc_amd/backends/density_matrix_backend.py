@@ -159,6 +159,11 @@ class DensityMatrixBackend(AQCBackend):
     measure on every qubit, so the errors attached to ``measure`` are in it, as they are in the sampling
     backend's cost; the compiler's circuit is untouched.  rho is evolved once per program and kept.
 
+    ``AdaptConfig(method="general_gradient")`` scores the pairs by the gradient of the noisy cost in the new
+    layer's angles: ``general_gradients`` reads one 4x4 environment per pair off rho in front of the layer
+    (``pair_environments``, aqc_dm_pair_envs) and prices every shifted candidate, with its errors, on the
+    host (``gradients.noisy_grads_from_envs``).  The starting circuit must be a product of one-qubit gates.
+
     ``heisenberg_sweep=True`` (opt-in): Rotosolve / Rotoselect cycles on the global or the local cost read
     every candidate of a gate off one 4x4 transition matrix between the forward-evolved prefix state and
     the observable pulled back through the suffix (``cached_rotations.DMHeisenbergSweep``) instead of
@@ -174,13 +179,14 @@ class DensityMatrixBackend(AQCBackend):
 
     def __init__(self, heisenberg_sweep=False, checkpoint_bytes=8 << 30):
         self._evolved = _Evolved()
+        self._evolved_left = _Evolved()  # rho in front of a candidate layer (pair_environments)
         self.heisenberg_sweep = bool(heisenberg_sweep)
         self.checkpoint_bytes = int(checkpoint_bytes)
         self._sweep = (0, [])
 
     # checkpoints pickle the whole compiler including its backend
     def __getstate__(self):
-        return {"_evolved": _Evolved(), "heisenberg_sweep": self.heisenberg_sweep,
+        return {"_evolved": _Evolved(), "_evolved_left": _Evolved(), "heisenberg_sweep": self.heisenberg_sweep,
                 "checkpoint_bytes": self.checkpoint_bytes, "_sweep": (0, [])}
 
     def sweep_states(self, n, count):
@@ -196,14 +202,18 @@ class DensityMatrixBackend(AQCBackend):
             states.append(DeviceDM(n))
         return states[:count]
 
-    def _run(self, compiler):
-        from ..noise import trajectory_program
-
+    @staticmethod
+    def _refuse_options(compiler):
         if getattr(compiler, "soften_global_cost", False):
             raise NotImplementedError("soften_global_cost is currently only implemented for AerMPSBackend")
         if getattr(compiler, "general_initial_state", False):
             raise NotImplementedError("DensityMatrixBackend does not support general_initial_state (its 2 n-qubit "
                                       "circuit): use QiskitSamplingBackend")
+
+    def _run(self, compiler):
+        from ..noise import trajectory_program
+
+        self._refuse_options(compiler)
         n = compiler.full_circuit.num_qubits
         _refuse_width(n, "DensityMatrixBackend")
         qc = without_classical_operations(compiler.full_circuit)
@@ -239,3 +249,34 @@ class DensityMatrixBackend(AQCBackend):
         sweep's input (``pair_entanglement_measures``)."""
         dev = self._run(compiler)
         return dev.pair_rdms(pairs) / dev.trace()
+
+    def pair_environments(self, compiler, pairs):
+        """(envs, trace, effects) for the noise-aware general gradient: rho evolved by the program of
+        ``full_circuit[:variational_circuit_range()[1]]`` (no measures; kept in a cache of its own, so the
+        cost's rho stays), Tr rho, the [n, 4] effects of reading all zeros pulled back through the
+        compiler's right-hand side and the error on ``measure`` (``noise.terminal_effects``), and complex
+        [len(pairs), 4, 4] environments of ``pairs`` (``DeviceDM.pair_envs``; not divided by the trace).
+        A candidate layer goes exactly between the two: its noisy cost is linear in the pair's R."""
+        from ..noise import terminal_effects, trajectory_program
+        from ..utils import circuit_operations as co
+
+        self._refuse_options(compiler)
+        full = compiler.full_circuit
+        n = full.num_qubits
+        _refuse_width(n, "DensityMatrixBackend")
+        noise_model = (getattr(compiler, "execute_kwargs", None) or {}).get("noise_model")
+        end = compiler.variational_circuit_range()[1]
+        effects = terminal_effects(n, full.data[end:], full, noise_model)
+        left = without_classical_operations(co.extract_inner_circuit(full, (0, end)))
+        rows, _, _ = trajectory_program(left, noise_model)
+        if getattr(self, "_evolved_left", None) is None:  # (a backend restored from an older checkpoint)
+            self._evolved_left = _Evolved()
+        dev = self._evolved_left.state(n, rows)
+        return dev.pair_envs(pairs, effects), dev.trace(), effects
+
+    def general_gradients(self, compiler):
+        """The noise-aware general gradient of every pair of ``compiler.coupling_map``
+        (``gradients.noisy_general_grad_of_pairs``)."""
+        from ..utils.gradients import noisy_general_grad_of_pairs
+
+        return noisy_general_grad_of_pairs(compiler)

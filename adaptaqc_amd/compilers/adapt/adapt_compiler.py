@@ -29,6 +29,7 @@ from pathlib import Path
 
 import numpy as np
 
+from ...backends.density_matrix_backend import DensityMatrixBackend
 from ...backends.python_default_backends import SV_SIM
 from ...circuit import QuantumCircuit, qasm2_dumps
 from ...mps_operations import mps_from_circuit
@@ -102,7 +103,10 @@ class AdaptCompiler(ApproximateCompiler):
             raise NotImplementedError("comm with shot-based tomography: sharding the tomography sweep is "
                                       "not supported")
         if self.adapt_config.method == "general_gradient":
-            if not self.is_aer_mps_backend:
+            # (not in the reference) the density-matrix backend scores the pairs under its noise model from
+            # one environment per pair (gradients.noisy_general_grad_of_pairs)
+            self.is_density_matrix_backend = isinstance(self.backend, DensityMatrixBackend)
+            if not (self.is_aer_mps_backend or self.is_density_matrix_backend):
                 raise ValueError("general_gradient method is only implemented for Aer MPS backend")
             self.generators, self.degeneracies = gr.get_generators_and_degeneracies(
                 self.layer_2q_gate, use_rotoselect, inverse=True)
@@ -419,7 +423,11 @@ class AdaptCompiler(ApproximateCompiler):
         return self.coupling_map[int(np.argmax(np.multiply(gradients, prio)))]
 
     def _get_all_qubit_pair_gradients(self):
-        """adapt_compiler.py:839-856 (starting circuit stripped by its length, as there)."""
+        """adapt_compiler.py:839-856 (starting circuit stripped by its length, as there).  On the
+        density-matrix backend: the noise-aware gradients (``comm`` is not used: every rank computes the
+        same list)."""
+        if getattr(self, "is_density_matrix_backend", False):
+            return self.backend.general_gradients(self)
         if self.starting_circuit is not None:
             rng = (0, len(self.full_circuit) - len(self.starting_circuit))
         else:

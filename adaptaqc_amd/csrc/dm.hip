@@ -39,6 +39,13 @@
 // local index j = r_q + 2 c_q: Tr(A^H (S_q (x) id)(B)) = sum S[j', j] T[j', j] for any one-qubit
 // superoperator S, so every candidate gate at a position, with its error, costs 16 host MACs.  It is the one
 // reader spread over workgroups (a partial per workgroup, a second launch adds them in order).
+//
+// Pair environments (gradients.noisy_general_grad_of_pairs).  A candidate layer on a pair sits directly in
+// front of a product measurement (|0><0| on every qubit pulled back through the errors on measure and a
+// product starting circuit's inverse: one Hermitian 2x2 effect E_q per qubit), so its noisy cost is linear
+// in R = Tr_rest((1 (x) E_rest) rho), the pair's 4x4 block with the other qubits' effects contracted in.
+// k_dm_pair_envs reads every pair's R off rho in one launch (spread over workgroups like k_dm_transition,
+// the weights prod E_q from two LDS tables); every generator, shift and error is 16x16 host arithmetic.
 #include <algorithm>
 #include <cmath>
 #include <complex>
@@ -381,6 +388,122 @@ __global__ __launch_bounds__(kThreads) void k_dm_pair_rdms(const cplx* __restric
     }
     out[(size_t)p * 16 + threadIdx.x] = aqc::cmk(sx, sy);
   }
+}
+
+// ---- pair environments ---------------------------------------------------------------------------------
+// R_p[a][b] = sum_{r, r'} rho[(a, r), (b, r')] prod_{q not in p} E_q[r'_q, r_q]: the pair's 4x4 block of rho
+// with the other qubits' effects contracted in.  r is the rest index (the n - 2 other qubits' row bits in
+// qubit order); r' differs from r only on the rest qubits whose effect has an off-diagonal (the mask gm in
+// rest bits, ng of them), so an item is (r, a), a < 2^ng, and a pair has 2^(n-2+ng) items of 16 entries.
+constexpr int kEnvMaxSplit = 256;  // workgroups of one pair
+
+// the workgroups a pair's items are spread over: an item per thread until 256 workgroups share the pair
+__host__ __device__ inline int env_split(int m, int ng) {
+  const int bits = m + ng - 8;  // log2(items / 256)
+  return bits <= 0 ? 1 : (bits >= 8 ? kEnvMaxSplit : 1 << bits);
+}
+
+// bit i of a to the position of the i-th set bit of mask
+__device__ __forceinline__ uint32_t deposit(uint32_t a, uint32_t mask) {
+  uint32_t out = 0;
+  while (mask) {
+    const uint32_t b = mask & (0u - mask);
+    if (a & 1u) out |= b;
+    a >>= 1;
+    mask ^= b;
+  }
+  return out;
+}
+
+// E[rp, r] of an effect g = (E00, E11, Re E01, Im E01); E10 = conj(E01)
+__device__ __forceinline__ cplx effect_at(const double* g, int rp, int r) {
+  return rp == r ? aqc::cmk(r ? g[1] : g[0], 0.0) : aqc::cmk(g[2], rp ? -g[3] : g[3]);
+}
+
+// part[(p * gridDim.x + s) * 32 ..]: workgroup s's share of pair p as 16 (re, im), index 4 a + b.  The weight
+// of an item is one product of two table entries: the rest bits split into a low half of hl = ceil(m / 2)
+// bits and a high half, each with its table in the LDS at (r_half, r'_half), of which only the entries that
+// can occur (2^(h + ng_half)) are filled.  Lanes take consecutive r: a wave's 16 loads are each contiguous
+// up to the splits the pair's two bits make.  A thread's items add in index order, then the wave butterfly
+// and the waves in order; k_dm_pair_envs_sum adds a pair's workgroups in order.
+__global__ __launch_bounds__(kThreads) void k_dm_pair_envs(const cplx* __restrict__ rho, int n,
+                                                           const int* __restrict__ pairs,
+                                                           const double* __restrict__ eff, uint32_t offdiag,
+                                                           double* __restrict__ part) {
+  extern __shared__ double2 env_tab[];
+  __shared__ double red[kThreads / 64][32];
+  const int p = blockIdx.y;
+  const int lo = min(pairs[2 * p], pairs[2 * p + 1]), hi = max(pairs[2 * p], pairs[2 * p + 1]);
+  const int m = n - 2, hl = (m + 1) >> 1, hh = m - hl;
+  // the qubit mask of the off-diagonals squeezed into rest bits
+  const uint32_t below_hi = (1u << hi) - 1u, below_lo = (1u << lo) - 1u;
+  uint32_t gm = ((offdiag >> (hi + 1)) << hi) | (offdiag & below_hi);
+  gm = ((gm >> (lo + 1)) << lo) | (gm & below_lo);
+  const int ng = __popc(gm);
+  const int nsplit = env_split(m, ng);
+  if ((int)blockIdx.x >= nsplit) return;  // (uniform: before any barrier)
+  cplx* tlo = reinterpret_cast<cplx*>(env_tab);
+  cplx* thi = tlo + ((size_t)1 << (2 * hl));
+  for (int half = 0; half < 2; ++half) {
+    const int h = half ? hh : hl, j0 = half ? hl : 0;
+    const uint32_t hmask = (1u << h) - 1u, gmh = (gm >> j0) & hmask;
+    cplx* tab = half ? thi : tlo;
+    const uint32_t count = 1u << (h + __popc(gmh));
+    for (uint32_t e = threadIdx.x; e < count; e += kThreads) {
+      const uint32_t rh = e & hmask, rph = (rh & ~gmh) | deposit(e >> h, gmh);
+      cplx w = aqc::cmk(1.0, 0.0);
+      for (int j = 0; j < h; ++j) {
+        int q = j0 + j;  // the rest bit's qubit: past the pair's two
+        q += q >= lo;
+        q += q >= hi;
+        w = aqc::cmul(w, effect_at(eff + 4 * q, (rph >> j) & 1, (rh >> j) & 1));
+      }
+      tab[rh | (rph << h)] = w;
+    }
+  }
+  __syncthreads();
+  const uint32_t items = 1u << (m + ng), chunk = items / (uint32_t)nsplit;
+  const uint32_t w0 = blockIdx.x * chunk, rmask = (1u << m) - 1u, lmask = (1u << hl) - 1u;
+  double acc[32];
+#pragma unroll
+  for (int e = 0; e < 32; ++e) acc[e] = 0.0;
+  for (uint32_t w = w0 + threadIdx.x; w < w0 + chunk; w += kThreads) {
+    const uint32_t r = w & rmask, rp = (r & ~gm) | deposit(w >> m, gm);
+    const cplx wt = aqc::cmul(tlo[(r & lmask) | ((rp & lmask) << hl)], thi[(r >> hl) | ((rp >> hl) << hh)]);
+    const uint32_t brow = insert_zero(insert_zero(r, lo), hi), bcol = insert_zero(insert_zero(rp, lo), hi);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const size_t colbase = (size_t)(bcol | ((uint32_t)(c & 1) << lo) | ((uint32_t)(c >> 1) << hi)) << n;
+#pragma unroll
+      for (int a = 0; a < 4; ++a) {
+        const cplx v = rho[colbase + (brow | ((uint32_t)(a & 1) << lo) | ((uint32_t)(a >> 1) << hi))];
+        acc[2 * (4 * a + c)] += wt.x * v.x - wt.y * v.y;
+        acc[2 * (4 * a + c) + 1] += wt.x * v.y + wt.y * v.x;
+      }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 32; ++e) acc[e] = wave_sum(acc[e]);
+  if ((threadIdx.x & 63) == 0)
+#pragma unroll
+    for (int e = 0; e < 32; ++e) red[threadIdx.x >> 6][e] = acc[e];
+  __syncthreads();
+  if (threadIdx.x < 32) {
+    double s = 0.0;
+    for (int w = 0; w < kThreads / 64; ++w) s += red[w][threadIdx.x];
+    part[((size_t)p * gridDim.x + blockIdx.x) * 32 + threadIdx.x] = s;
+  }
+}
+
+// out[p][e] = sum_s part[p][s][e] over the pair's own workgroups, s ascending (a workgroup of 32 per pair)
+__global__ void k_dm_pair_envs_sum(const double* __restrict__ part, int n, const int* __restrict__ pairs,
+                                   uint32_t offdiag, int stride, double* __restrict__ out) {
+  const int p = blockIdx.x;
+  const uint32_t own = (1u << pairs[2 * p]) | (1u << pairs[2 * p + 1]);
+  const int nsplit = env_split(n - 2, __popc(offdiag & ~own));
+  double s = 0.0;
+  for (int b = 0; b < nsplit; ++b) s += part[((size_t)p * stride + b) * 32 + threadIdx.x];
+  out[(size_t)p * 32 + threadIdx.x] = s;
 }
 
 // ---- host planning -----------------------------------------------------------------------------------
@@ -1008,6 +1131,62 @@ int aqc_dm_pair_rdms(aqc_dm_t h, const int* pairs, int npairs, double* out) {
   AQC_CHECK_LAUNCH();
   AQC_HIP_CHECK(hipMemcpyAsync(out, buf + pb, ob, hipMemcpyDeviceToHost, h->stream));
   AQC_HIP_CHECK(hipStreamSynchronize(h->stream));
+  return AQC_OK;
+}
+
+int aqc_dm_pair_envs(aqc_dm_t h, const int* pairs, int npairs, const double* effects, double* out) {
+  AQC_REQUIRE(h && pairs && out && npairs >= 0 && npairs <= kMaxPairs, "aqc_dm_pair_envs: bad arguments");
+  AQC_REQUIRE(h->n >= 2, "aqc_dm_pair_envs: needs at least 2 qubits");
+  const int n = h->n, m = n - 2;
+  for (int p = 0; p < npairs; ++p) {
+    const int a = pairs[2 * p], b = pairs[2 * p + 1];
+    AQC_REQUIRE(a >= 0 && a < n && b >= 0 && b < n && a != b, "aqc_dm_pair_envs: bad pair");
+  }
+  double eff[kMaxQubits][4];
+  uint32_t offdiag = 0;  // the qubits whose effect has an off-diagonal
+  for (int q = 0; q < n; ++q)
+    for (int c = 0; c < 4; ++c) {
+      eff[q][c] = effects ? effects[4 * q + c] : (c < 2 ? 1.0 : 0.0);
+      AQC_REQUIRE(std::isfinite(eff[q][c]), "aqc_dm_pair_envs: an effect is not finite");
+      if (c >= 2 && eff[q][c] != 0.0) offdiag |= 1u << q;
+    }
+  if (npairs == 0) return AQC_OK;
+  int split = 1;  // the grid's: the largest of the pairs'
+  double items = 0.0;
+  for (int p = 0; p < npairs; ++p) {
+    const int ng = __builtin_popcount(offdiag & ~((1u << pairs[2 * p]) | (1u << pairs[2 * p + 1])));
+    split = std::max(split, env_split(m, ng));
+    items += std::ldexp(1.0, m + ng);
+  }
+  const size_t pb = aqc::up256((size_t)2 * npairs * sizeof(int)), eb = aqc::up256(sizeof(eff));
+  const size_t ob = aqc::up256((size_t)npairs * 16 * sizeof(cplx));
+  const size_t qb = split > 1 ? (size_t)npairs * split * 32 * sizeof(double) : 0;
+  char* buf = nullptr;
+  if (int rc = dm_buf(h, pb + eb + ob + qb, &buf)) return rc;
+  const int* d_pairs = (const int*)buf;
+  const double* d_eff = (const double*)(buf + pb);
+  double* d_out = (double*)(buf + pb + eb);
+  double* d_part = split > 1 ? (double*)(buf + pb + eb + ob) : d_out;
+  AQC_HIP_CHECK(hipMemcpyAsync(buf, pairs, (size_t)2 * npairs * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  AQC_HIP_CHECK(hipMemcpyAsync(buf + pb, eff, sizeof(eff), hipMemcpyHostToDevice, h->stream));
+  // the two weight tables: 4^ceil(m / 2) + 4^floor(m / 2) complex words, 80 KB at 13 qubits
+  const int hl = (m + 1) / 2, hh = m - hl;
+  const size_t lds = (((size_t)1 << (2 * hl)) + ((size_t)1 << (2 * hh))) * sizeof(cplx);
+  if (lds > 48 * 1024)
+    AQC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dm_pair_envs),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  aqc::KernelTimer::begin(h->stream, "dm_pair_envs", 256.0 * items, 136.0 * items);  // 16 + 1 complex MACs an item
+  hipLaunchKernelGGL(k_dm_pair_envs, dim3(split, npairs), dim3(kThreads), lds, h->stream, h->rho, n, d_pairs, d_eff,
+                     offdiag, d_part);
+  aqc::KernelTimer::end(h->stream);
+  AQC_CHECK_LAUNCH();
+  if (split > 1) {
+    hipLaunchKernelGGL(k_dm_pair_envs_sum, dim3(npairs), dim3(32), 0, h->stream, (const double*)d_part, n, d_pairs,
+                       offdiag, split, d_out);
+    AQC_CHECK_LAUNCH();
+  }
+  AQC_HIP_CHECK(hipMemcpyAsync(out, d_out, (size_t)npairs * 16 * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
+  AQC_HIP_CHECK(hipStreamSynchronize(h->stream));  // (pairs and eff are read by the copies until here)
   return AQC_OK;
 }
 

@@ -251,6 +251,23 @@ class DeviceDM:
             _lib.check(self._l.aqc_dm_pair_rdms(self.h, _lib.ptr(pairs), len(pairs) // 2, _lib.ptr(out)))
         return out.reshape(-1, 4, 4)
 
+    def pair_envs(self, pairs, effects=None):
+        """complex [npairs, 4, 4]: every pair's environment R = Tr_rest((1 (x) E_rest) rho)
+        (aqc_dm_pair_envs), index 2 bit_hi + bit_lo as ``pair_rdms``.  ``effects``: float64 [n, 4], qubit
+        q's Hermitian effect as (E00, E11, Re E01, Im E01) (``noise.terminal_effects``; a pair's own
+        entries are ignored), or None for identity effects, which give the RDMs.  For any channel L on
+        the pair, Tr(((x) E_q) (L (x) id)(rho)) = Tr((E_hi (x) E_lo) L(R))."""
+        pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1))
+        eff = None
+        if effects is not None:
+            eff = np.ascontiguousarray(effects, dtype=np.float64)
+            if eff.shape != (self.n, 4):
+                raise ValueError(f"pair_envs: effects must have shape {(self.n, 4)}")
+        out = np.zeros(len(pairs) // 2 * 16, dtype=np.complex128)
+        if len(pairs):
+            _lib.check(self._l.aqc_dm_pair_envs(self.h, _lib.ptr(pairs), len(pairs) // 2, _lib.ptr(eff), _lib.ptr(out)))
+        return out.reshape(-1, 4, 4)
+
 
 DM_PLAN_COUNTS = ("segments", "steps", "rows", "tile_bits")
 

@@ -367,6 +367,88 @@ def candidate_superoperator(matrix, name, qubit, noise_model):
     return s
 
 
+def _pair_frame(matrix, qubits, lo):
+    """A 2x2 operator on one of a pair's qubits, or a 4x4 one on both (index 2 b(second listed) + b(first
+    listed)), as a 4x4 matrix at the pair's index 2 bit_hi + bit_lo."""
+    m = np.asarray(matrix, dtype=complex)
+    if m.shape == (2, 2):
+        return np.kron(np.eye(2), m) if qubits[0] == lo else np.kron(m, np.eye(2))
+    if qubits[0] == lo:
+        return m
+    swap = [0, 2, 1, 3]
+    return m[np.ix_(swap, swap)]
+
+
+def layer_superoperator(circuit, qubits, noise_model):
+    """The 16x16 superoperator of the two-qubit ``circuit`` placed on ``qubits`` (its qubit 0 on
+    ``qubits[0]``): its gates composed with every channel that ``noise_model.channels(name, qubits)``
+    attaches to them, in ``trajectory_program``'s order (a gate, then its errors in the gate's qubit order,
+    or its one correlated error).  Index (2 r_hi + r_lo) + 4 (2 c_hi + c_lo) with lo / hi the smaller /
+    larger of ``qubits``: x <- S x on R.reshape(-1, order="F") of a pair environment
+    (``DeviceDM.pair_envs``).  ``noise_model`` None: the lifted unitary."""
+    from .circuit import decompose, qubit_indices
+
+    qubits = (int(qubits[0]), int(qubits[1]))
+    if qubits[0] == qubits[1]:
+        raise ValueError("layer_superoperator: two different qubits")
+    lo = min(qubits)
+
+    def lifted(mats, qs):
+        return sum(np.kron(f.conj(), f) for f in (_pair_frame(k, qs, lo) for k in mats))
+
+    s = np.eye(16, dtype=complex)
+    for ins in circuit.data:
+        name = ins.operation.name
+        if name in ("barrier", "id", "delay"):
+            continue
+        if name == "measure":
+            raise ValueError("layer_superoperator: a circuit of gates, without measures")
+        qs = tuple(qubits[i] for i in qubit_indices(circuit, ins))
+        for matrix, q in decompose(ins, qs):
+            s = lifted([matrix], q) @ s
+        if noise_model is not None:
+            for q, error in noise_model.channels(name, qs):
+                s = lifted(error.kraus, q if error.correlated else (q,)) @ s
+    return s
+
+
+def terminal_effects(n, rhs_instructions, circuit, noise_model):
+    """float64 [n, 4]: per qubit (E00, E11, Re E01, Im E01) of the effect that reading 0 on it has in front
+    of ``rhs_instructions`` (instructions of ``circuit``: what a compiler keeps to the right of its
+    variational range): |0><0| pulled back through the adjoint of the error on ``measure`` and then, last
+    instruction first, through every gate and the error attached to it.  Every instruction must act on one
+    qubit (measures, barriers, ``id`` and ``delay`` aside): a starting circuit with an entangling gate
+    leaves no product of effects and raises NotImplementedError.  ``DeviceDM.pair_envs`` takes the result."""
+    from .circuit import op_matrix, qubit_indices
+
+    def adjoint(name, q, e):
+        if noise_model is None:
+            return e
+        for _, error in noise_model.channels(name, (q,)):
+            e = sum(k.conj().T @ e @ k for k in error.kraus)
+        return e
+
+    n = int(n)
+    eff = []
+    for q in range(n):
+        e = np.zeros((2, 2), dtype=complex)
+        e[0, 0] = 1.0
+        eff.append(adjoint("measure", q, e))
+    for ins in reversed(list(rhs_instructions)):
+        name = ins.operation.name
+        if name in ("barrier", "id", "delay", "measure"):
+            continue
+        qs = qubit_indices(circuit, ins)
+        if len(qs) != 1:
+            raise NotImplementedError(
+                f"terminal_effects: the {len(qs)}-qubit gate {name!r} after the variational range leaves no product "
+                "of one-qubit effects: the noise-aware general_gradient needs a starting_circuit of one-qubit "
+                "gates (or none)")
+        u = np.asarray(op_matrix(ins.operation), dtype=complex)
+        eff[qs[0]] = u.conj().T @ adjoint(name, qs[0], eff[qs[0]]) @ u
+    return np.array([(e[0, 0].real, e[1, 1].real, e[0, 1].real, e[0, 1].imag) for e in eff])
+
+
 def trajectory_program(circuit, noise_model):
     """(rows, n_events, measured): the flat program of aqc_sv_traj_sample for ``circuit`` under
     ``noise_model``.  Each gate of ``device_ops(circuit)`` is a gate row; after a gate that carries an

@@ -211,8 +211,98 @@ def get_generator(ansatz: QuantumCircuit, index: int, op: str):
     return gen
 
 
+def shifted_layers(layer: QuantumCircuit, rotoselect: bool, shift: float):
+    """The candidate circuits L_{i,op}(shift): ``layer`` with every rotation at angle 0 under its own name and
+    rotation i replaced by op(shift), for every rotation i and every op in rx, ry, rz (only i's own name
+    without ``rotoselect``), in ``get_generators_and_degeneracies``'s order."""
+    from ..circuit import CircuitInstruction
+    from .circuit_operations import create_1q_gate
+
+    for ins in layer.data:
+        if ins.operation.name not in PARAMETERISED + ("cx",):
+            raise ValueError("Circuit must only contain rx, ry, rz and cx gates")
+    zero = QuantumCircuit(2)
+    for ins in layer.data:
+        name = ins.operation.name
+        op = create_1q_gate(name, 0.0) if name in PARAMETERISED else ins.operation.copy()
+        zero.data.append(CircuitInstruction(op, list(ins.qubits)))
+    out = []
+    for i, ins in enumerate(layer.data):
+        if ins.operation.name not in PARAMETERISED:
+            continue
+        for op in (PARAMETERISED if rotoselect else (ins.operation.name,)):
+            qc = QuantumCircuit(2)
+            qc.data = list(zero.data)
+            qc.data[i] = CircuitInstruction(create_1q_gate(op, float(shift)), list(ins.qubits))
+            out.append(qc)
+    return out
+
+
+def noisy_grads_from_envs(envs, trace, effects, layer, coupling_map, noise_model, rotoselect):
+    """The noise-aware general gradient of every ordered pair (c, t) of ``coupling_map`` from the pairs'
+    environments (host only).
+
+    ``envs``: complex [len(coupling_map), 4, 4], R of each pair at the index 2 bit_hi + bit_lo
+    (``DeviceDM.pair_envs``; not divided by the trace); ``trace``: Tr rho; ``effects``: [n, 4] as
+    ``noise.terminal_effects``.  With S the superoperator of a candidate circuit on (c, t) under
+    ``noise_model`` (``noise.layer_superoperator``), C = 1 - Re Tr((E_hi (x) E_lo) S(R)) / Tr rho, and
+    g_{i,op} = [C(L_{i,op}(+pi/2)) - C(L_{i,op}(-pi/2))] / 2 is dC/dtheta at 0 exactly (C is a + b cos theta +
+    c sin theta in one rotation angle whatever fixed channels follow).  Returns sqrt(sum_{i,op} g^2) per
+    pair; with ``noise_model`` None that is the reference's sqrt(sum_k deg_k g_k^2)."""
+    from ..noise import layer_superoperator
+
+    envs = np.asarray(envs, dtype=complex).reshape(-1, 4, 4)
+    effects = np.asarray(effects, dtype=float)
+    if len(envs) != len(coupling_map):
+        raise ValueError("noisy_grads_from_envs: one environment per pair of the coupling map")
+    plus = shifted_layers(layer, rotoselect, np.pi / 2)
+    minus = shifted_layers(layer, rotoselect, -np.pi / 2)
+    # without errors attached to particular qubits the maps depend on the pair's orientation alone
+    local = noise_model is not None and bool(getattr(noise_model, "_local", None))
+    cache = {}
+
+    def half_differences(c, t):
+        key = (c, t) if local else c < t
+        if key not in cache:
+            cache[key] = np.stack([(layer_superoperator(p, (c, t), noise_model)
+                                    - layer_superoperator(m, (c, t), noise_model)) / 2
+                                   for p, m in zip(plus, minus)]) if plus else np.zeros((0, 16, 16), dtype=complex)
+        return cache[key]
+
+    def matrix(e):
+        return np.array([[e[0], e[2] + 1j * e[3]], [e[2] - 1j * e[3], e[1]]])
+
+    out = []
+    for (c, t), env in zip(coupling_map, envs):
+        c, t = int(c), int(t)
+        lo, hi = min(c, t), max(c, t)
+        evec = np.kron(matrix(effects[hi]), matrix(effects[lo])).reshape(-1)  # Tr(E X) = evec . vec(X)
+        g = -np.real(half_differences(c, t) @ env.reshape(-1, order="F") @ evec) / trace
+        out.append(float(np.sqrt(np.sum(g * g))))
+    return out
+
+
+def noisy_general_grad_of_pairs(compiler):
+    """The noise-aware general gradient of every pair of ``compiler.coupling_map`` on a
+    ``DensityMatrixBackend``: one reader over the evolved rho (``pair_environments``: one
+    ``DeviceDM.pair_envs`` call over the unordered pairs) and host arithmetic per candidate
+    (``noisy_grads_from_envs``); a pair listed in both orientations shares its environment."""
+    cmap = [(int(c), int(t)) for c, t in compiler.coupling_map]
+    if not cmap:
+        return []
+    unordered = sorted({(min(c, t), max(c, t)) for c, t in cmap})
+    envs, trace, effects = compiler.backend.pair_environments(compiler, unordered)
+    where = {p: k for k, p in enumerate(unordered)}
+    envs = np.stack([envs[where[(min(c, t), max(c, t))]] for c, t in cmap])
+    noise_model = (getattr(compiler, "execute_kwargs", None) or {}).get("noise_model")
+    return noisy_grads_from_envs(envs, trace, effects, compiler.layer_2q_gate, cmap, noise_model,
+                                 compiler.use_rotoselect)
+
+
 __all__ = [
     "general_grad_of_pairs",
+    "noisy_grads_from_envs",
+    "noisy_general_grad_of_pairs",
     "get_generators_and_degeneracies",
     "get_generator",
     "circuit_unitary",

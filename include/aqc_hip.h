@@ -468,6 +468,19 @@ int aqc_dm_pauli_expect(aqc_dm_t h, const uint8_t* codes, int nterms, const doub
    2 bit_hi + bit_lo, hi the pair's larger qubit; the sum over the 2^(n-2) values of the other qubits in a
    fixed order, one workgroup per pair.  n >= 2, at most 4096 pairs. */
 int aqc_dm_pair_rdms(aqc_dm_t h, const int* pairs, int npairs, double* out);
+/* out[p] = the 4x4 environment of pair p in aqc_dm_pair_rdms's layout: with r the other qubits' row bits
+   and r' their column bits,
+     R[a][b] = sum_{r, r'} rho[(a, r), (b, r')] prod_{q not in p} E_q[r'_q, r_q] = Tr_rest((1 (x) E_rest) rho),
+   so that Tr(((x)_q E_q) (Lambda (x) id)(rho)) = Tr((E_hi (x) E_lo) Lambda(R)) for any channel Lambda on the
+   pair: every candidate gate on the pair, with its errors, in front of a product measurement is priced on
+   the host from R.  effects: n x 4 doubles, (E00, E11, Re E01, Im E01) of qubit q's Hermitian effect (the
+   entries of a pair's own qubits are ignored), or NULL for identity effects (R is then the RDM).  r' runs
+   only over the qubits whose effect has a nonzero off-diagonal: ng of them cost a pair 16 x 2^(n-2+ng)
+   entries, all-diagonal effects the bytes of aqc_dm_pair_rdms.  A pair is spread over up to 256 workgroups
+   (256 items each at first), which write partials that a second pass adds in order: no atomics, two
+   calls give the same bits.  rho is any matrix (aqc_dm_set) and is not changed.  n >= 2, at most 4096
+   pairs; AQC_ERR_ARG also for an effect that is not finite. */
+int aqc_dm_pair_envs(aqc_dm_t h, const int* pairs, int npairs, const double* effects, double* out);
 
 /* ---- Pauli-string expectation values: replaces circuit_operations_pauli_ops.py:60-100 -------------
    (expectation_value_of_pauli_operator, which runs one rotated circuit per term).
