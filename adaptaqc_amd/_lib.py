@@ -59,7 +59,7 @@ EXPORTS = (
     "aqc_dm_create", "aqc_dm_destroy", "aqc_dm_reset", "aqc_dm_apply", "aqc_dm_plan", "aqc_dm_get", "aqc_dm_trace0",
     "aqc_dm_diag_sv", "aqc_dm_pauli_expect", "aqc_dm_pair_rdms",
     "aqc_dm_apply_adjoint", "aqc_dm_plan_adjoint", "aqc_dm_set", "aqc_dm_set_diag", "aqc_dm_copy", "aqc_dm_transition",
-    "aqc_dm_pair_envs",
+    "aqc_dm_pair_envs", "aqc_dm_pair_transitions", "aqc_dm_pair_transitions_plan",
 )
 
 
@@ -204,6 +204,8 @@ _SIGS = {
     "aqc_dm_copy": ([_P, _P], _I),
     "aqc_dm_transition": ([_P, _P, _I, _P], _I),
     "aqc_dm_pair_envs": ([_P, _P, _I, _P, _P], _I),
+    "aqc_dm_pair_transitions": ([_P, _P, _P, _I, _P], _I),
+    "aqc_dm_pair_transitions_plan": ([_I, _I, _IP], _I),
 }
 
 

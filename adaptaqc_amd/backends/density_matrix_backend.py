@@ -176,18 +176,42 @@ class DensityMatrixBackend(AQCBackend):
     heisenberg_sweep = False
     checkpoint_bytes = 8 << 30
     _sweep = (0, ())
+    pair_transitions = False
+    gradient_cost = "global"
+    _observables = None
+    backward_passes = 0
 
-    def __init__(self, heisenberg_sweep=False, checkpoint_bytes=8 << 30):
+    def __init__(self, heisenberg_sweep=False, checkpoint_bytes=8 << 30, pair_transitions=False,
+                 gradient_cost="global"):
+        if not (isinstance(pair_transitions, bool) or pair_transitions == "always"):
+            raise ValueError(f"DensityMatrixBackend: pair_transitions must be False, True or 'always', not "
+                             f"{pair_transitions!r}")
+        if gradient_cost not in ("global", "local", "compiler"):
+            raise ValueError(f"DensityMatrixBackend: gradient_cost must be 'global', 'local' or 'compiler', not "
+                             f"{gradient_cost!r}")
         self._evolved = _Evolved()
         self._evolved_left = _Evolved()  # rho in front of a candidate layer (pair_environments)
         self.heisenberg_sweep = bool(heisenberg_sweep)
         self.checkpoint_bytes = int(checkpoint_bytes)
         self._sweep = (0, [])
+        self.pair_transitions = pair_transitions
+        self.gradient_cost = gradient_cost
+        self._observables = {}    # cost kind -> (key, DeviceDM): the observable pulled back through the right-hand side
+        self.backward_passes = 0  # the run_adjoint passes that made them
+        if gradient_cost == "local":
+            self._refuse_local_without_transitions()
+
+    def _refuse_local_without_transitions(self):
+        if not self.pair_transitions:
+            raise ValueError("DensityMatrixBackend: gradient_cost='local' needs pair_transitions=True (or 'always'): "
+                             "the environments route reads the global cost only")
 
     # checkpoints pickle the whole compiler including its backend
     def __getstate__(self):
         return {"_evolved": _Evolved(), "_evolved_left": _Evolved(), "heisenberg_sweep": self.heisenberg_sweep,
-                "checkpoint_bytes": self.checkpoint_bytes, "_sweep": (0, [])}
+                "checkpoint_bytes": self.checkpoint_bytes, "_sweep": (0, []),
+                "pair_transitions": self.pair_transitions, "gradient_cost": self.gradient_cost,
+                "_observables": {}, "backward_passes": 0}
 
     def sweep_states(self, n, count):
         """``count`` device matrices of n qubits for the Heisenberg sweep, kept from cycle to cycle."""
@@ -257,26 +281,109 @@ class DensityMatrixBackend(AQCBackend):
         compiler's right-hand side and the error on ``measure`` (``noise.terminal_effects``), and complex
         [len(pairs), 4, 4] environments of ``pairs`` (``DeviceDM.pair_envs``; not divided by the trace).
         A candidate layer goes exactly between the two: its noisy cost is linear in the pair's R."""
-        from ..noise import terminal_effects, trajectory_program
-        from ..utils import circuit_operations as co
+        from ..noise import terminal_effects
 
+        n, full, end, noise_model = self._layer_context(compiler)
+        effects = terminal_effects(n, full.data[end:], full, noise_model)  # (refuses before any device work)
+        dev = self._left_state(n, full, end, noise_model)
+        return dev.pair_envs(pairs, effects), dev.trace(), effects
+
+    def _layer_context(self, compiler):
+        """(n, full_circuit, the end of the variational range, the noise model), after the backend's refusals."""
         self._refuse_options(compiler)
         full = compiler.full_circuit
         n = full.num_qubits
         _refuse_width(n, "DensityMatrixBackend")
         noise_model = (getattr(compiler, "execute_kwargs", None) or {}).get("noise_model")
-        end = compiler.variational_circuit_range()[1]
-        effects = terminal_effects(n, full.data[end:], full, noise_model)
+        return n, full, compiler.variational_circuit_range()[1], noise_model
+
+    def _left_state(self, n, full, end, noise_model):
+        """rho in front of a candidate layer: evolved by the program of ``full[:end]``, kept in a cache of its own."""
+        from ..noise import trajectory_program
+        from ..utils import circuit_operations as co
+
         left = without_classical_operations(co.extract_inner_circuit(full, (0, end)))
         rows, _, _ = trajectory_program(left, noise_model)
         if getattr(self, "_evolved_left", None) is None:  # (a backend restored from an older checkpoint)
             self._evolved_left = _Evolved()
-        dev = self._evolved_left.state(n, rows)
-        return dev.pair_envs(pairs, effects), dev.trace(), effects
+        return self._evolved_left.state(n, rows)
+
+    def _pulled_back_observable(self, n, full, end, noise_model, cost):
+        """M = Lambda^dag(O) on the device: the observable of ``cost`` pulled back through the program of
+        ``full[end:]`` and the errors on every qubit's measure.  It depends on the right-hand side, the noise
+        model and the cost alone: kept per cost, keyed by the program's bytes, so a compile makes one backward
+        pass (``backward_passes`` counts them)."""
+        from ..device import DeviceDM
+        from ..utils.cached_rotations import load_cost_observable, noisy_rows
+
+        rows = noisy_rows(full, end, len(full.data), noise_model, measures=True)
+        key = (n, rows.tobytes())
+        if self._observables is None:  # (a backend restored from an older checkpoint)
+            self._observables = {}
+        held = self._observables.get(cost)
+        if held is not None and held[0] == key:
+            return held[1]
+        dev = held[1] if held is not None and held[0][0] == n else DeviceDM(n)
+        self._observables.pop(cost, None)
+        load_cost_observable(dev, cost)
+        dev.run_adjoint(rows)
+        self.backward_passes += 1
+        self._observables[cost] = (key, dev)
+        return dev
+
+    def pair_transition_matrices(self, compiler, pairs, cost="global"):
+        """(T, trace): complex [len(pairs), 16, 16] transition matrices of ``pairs`` between M, the observable
+        of ``cost`` ("global": |0...0><0...0|, "local": diag(popcount / n)) pulled back through everything behind
+        the variational range, and rho in front of a candidate layer (``pair_environments``'s cached state);
+        Tr rho.  A two-qubit circuit with superoperator S (``noise.layer_superoperator``) placed there has
+        Tr(O rho_final) / Tr rho = Re sum(S * T) / trace: the local cost, or 1 minus the global cost."""
+        if cost not in ("global", "local"):
+            raise ValueError("pair_transition_matrices: cost must be 'global' or 'local'")
+        n, full, end, noise_model = self._layer_context(compiler)
+        rho = self._left_state(n, full, end, noise_model)
+        obs = self._pulled_back_observable(n, full, end, noise_model, cost)
+        return obs.pair_transitions(rho, pairs), rho.trace()
+
+    def candidate_layer_costs(self, compiler, pair, circuits, cost="global"):
+        """The exact noisy ``cost`` of every two-qubit circuit of ``circuits`` placed on ``pair`` (its qubit 0 on
+        ``pair[0]``) at the end of the variational range, errors included: one reader call, then 16x16 host
+        arithmetic per circuit -- rho is not evolved."""
+        from ..noise import layer_superoperator
+
+        pair = (int(pair[0]), int(pair[1]))
+        noise_model = (getattr(compiler, "execute_kwargs", None) or {}).get("noise_model")
+        trans, trace = self.pair_transition_matrices(compiler, [pair], cost)
+        vals = [float(np.sum(layer_superoperator(qc, pair, noise_model) * trans[0]).real / trace) for qc in circuits]
+        return [1.0 - v for v in vals] if cost == "global" else vals
+
+    def _gradient_kind(self, compiler):
+        """The cost whose gradient ``general_gradients`` takes."""
+        kind = self.gradient_cost
+        if kind == "compiler":
+            kind = "local" if getattr(compiler, "optimise_local_cost", False) else "global"
+        if kind == "local":
+            self._refuse_local_without_transitions()
+        return kind
+
+    @staticmethod
+    def _product_right_hand_side(compiler):
+        """Whether every gate behind the variational range acts on one qubit (``terminal_effects`` applies)."""
+        from ..circuit import qubit_indices
+
+        full = compiler.full_circuit
+        end = compiler.variational_circuit_range()[1]
+        return all(len(qubit_indices(full, ins)) == 1 for ins in full.data[end:]
+                   if ins.operation.name not in ("barrier", "id", "delay", "measure"))
 
     def general_gradients(self, compiler):
-        """The noise-aware general gradient of every pair of ``compiler.coupling_map``
-        (``gradients.noisy_general_grad_of_pairs``)."""
-        from ..utils.gradients import noisy_general_grad_of_pairs
+        """The noise-aware general gradient of every pair of ``compiler.coupling_map``: from the pairs'
+        environments (``gradients.noisy_general_grad_of_pairs``), or with ``pair_transitions`` from their
+        transition matrices (``gradients.noisy_transition_grad_of_pairs``) when the right-hand side entangles,
+        the gradient is the local cost's, or ``pair_transitions="always"``."""
+        from ..utils.gradients import noisy_general_grad_of_pairs, noisy_transition_grad_of_pairs
 
+        kind = self._gradient_kind(compiler)
+        mode = self.pair_transitions
+        if mode == "always" or (mode and (kind == "local" or not self._product_right_hand_side(compiler))):
+            return noisy_transition_grad_of_pairs(compiler, kind)
         return noisy_general_grad_of_pairs(compiler)

@@ -46,12 +46,21 @@
 // in R = Tr_rest((1 (x) E_rest) rho), the pair's 4x4 block with the other qubits' effects contracted in.
 // k_dm_pair_envs reads every pair's R off rho in one launch (spread over workgroups like k_dm_transition,
 // the weights prod E_q from two LDS tables); every generator, shift and error is 16x16 host arithmetic.
+//
+// Pair transitions (gradients.noisy_grads_from_transitions).  k_dm_transition's two-qubit version: for a pair,
+// T[j', j] = sum_o conj(A[j', o]) B[j, o] at the pair's local index j = (r_lo + 2 r_hi) + 4 (c_lo + 2 c_hi), o the
+// other 2n - 4 index bits, so Tr(A^H (S (x) id)(B)) = sum S[j', j] T[j', j] for any two-qubit superoperator S.
+// With A an observable pulled back through any right-hand side and B the state in front of a candidate layer, it
+// prices every candidate on the pair, whatever follows it and for either cost.  Per pair a 16 x 16 x 4^(n-2)
+// complex GEMM: k_dm_pair_transitions runs it on the FP64 matrix cores (four real v_mfma_f64_16x16x4_f64 per
+// four values of o), a wave on a contiguous run of o, a pair spread over workgroups like k_dm_pair_envs.
 #include <algorithm>
 #include <cmath>
 #include <complex>
 #include <cstring>
 #include <vector>
 
+#include "aqc_gemm.h"
 #include "aqc_internal.h"
 #include "kraus_group.h"
 #include "pair_draw.h"
@@ -504,6 +513,95 @@ __global__ void k_dm_pair_envs_sum(const double* __restrict__ part, int n, const
   double s = 0.0;
   for (int b = 0; b < nsplit; ++b) s += part[((size_t)p * stride + b) * 32 + threadIdx.x];
   out[(size_t)p * 32 + threadIdx.x] = s;
+}
+
+// ---- pair transitions ----------------------------------------------------------------------------------
+// T_p[j'][j] = sum_o conj(A[j', o]) B[j, o]: j = (r_lo + 2 r_hi) + 4 (c_lo + 2 c_hi) the pair's local index (index
+// bits lo, hi, n + lo, n + hi), o the other 2n - 4 index bits in ascending order, K = 4^(n-2) values.
+constexpr int kTransMaxSplit = 256;   // workgroups of one pair
+constexpr int kTransUnroll = 4;       // MFMA steps (of 4 values of o) whose operands are requested together
+constexpr int kTransMaxGroups = 8192; // workgroups of one launch that write a partial (4 KB each)
+
+// the workgroups a pair's K values of o are spread over: 256 values (64 a wave) each until 256 workgroups
+// share the pair; fewer when the pairs alone fill the device (the partials stay within 32 MB)
+inline int trans_split(int n, int npairs) {
+  const int bits = 2 * (n - 2) - 8;  // log2(K / 256)
+  int split = bits <= 0 ? 1 : (bits >= 8 ? kTransMaxSplit : 1 << bits);
+  while (split > 1 && (long long)split * npairs > kTransMaxGroups) split >>= 1;
+  return split;
+}
+
+// part[(p * gridDim.x + s) * 256 + 16 j' + j]: workgroup s's share of pair p.  The workgroup's K / gridDim.x
+// values of o go to its waves as contiguous runs (at least 4: with K < 16 only the first waves have work).  A
+// step is one 16 x 16 x 4 product: lane l feeds (j' = l & 15, o = o0 + (l >> 4)) of A and the same entry of B (the
+// MFMA's A operand is [m = l & 15][k = l >> 4], its B operand [k = l >> 4][n = l & 15]); Re T accumulates
+// ar br + ai bi, Im T ar bi - ai br, as four real MFMAs into two accumulators.  A lane whose o is past the run's
+// end feeds zeros.  A wave walks its run upwards, kTransUnroll steps (16 consecutive o) requested at once: for
+// each of the 16 values of j the 16 entries are one contiguous run of index space wherever the pair's bits
+// leave one (256 B when lo >= 4; with lo < 4 the run breaks at bit lo and the neighbouring j fill the gap), so
+// every cache line a wave touches is used up by that iteration or the next and never revisited.
+// The result tile holds T[(l >> 4) + 4 reg][l & 15]; the waves' tiles add in order in the LDS, and
+// k_dm_pair_transitions_sum adds a pair's workgroups in order.
+__global__ __launch_bounds__(kThreads) void k_dm_pair_transitions(const cplx* __restrict__ A,
+                                                                  const cplx* __restrict__ B, int n,
+                                                                  const int* __restrict__ pairs,
+                                                                  cplx* __restrict__ part) {
+  __shared__ double red[kThreads / 64][8][64];
+  const int p = blockIdx.y;
+  const int lo = min(pairs[2 * p], pairs[2 * p + 1]), hi = max(pairs[2 * p], pairs[2 * p + 1]);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lk = lane >> 4;
+  const uint32_t K = 1u << (2 * n - 4), chunk = K / gridDim.x;  // (gridDim.x is a power of two <= K)
+  const uint32_t run = max(4u, chunk / (uint32_t)(kThreads / 64));
+  const uint32_t w0 = blockIdx.x * chunk;
+  const uint32_t begin = min(w0 + (uint32_t)wave * run, w0 + chunk), end = min(begin + run, w0 + chunk);
+  const uint32_t jbits = ((uint32_t)(li & 1) << lo) | ((uint32_t)((li >> 1) & 1) << hi) |
+                         ((uint32_t)((li >> 2) & 1) << (n + lo)) | ((uint32_t)(li >> 3) << (n + hi));
+  aqc::d4_t sr = {0, 0, 0, 0}, si = {0, 0, 0, 0};
+  for (uint32_t o0 = begin; o0 < end; o0 += 4 * kTransUnroll) {  // (uniform per wave)
+    cplx a[kTransUnroll], b[kTransUnroll];
+#pragma unroll
+    for (int s = 0; s < kTransUnroll; ++s) {
+      const uint32_t o = o0 + 4 * s + lk;
+      a[s] = b[s] = aqc::cmk(0.0, 0.0);
+      if (o < end) {
+        const size_t at = insert_zero(insert_zero(insert_zero(insert_zero(o, lo), hi), n + lo), n + hi) | jbits;
+        a[s] = A[at];
+        b[s] = B[at];
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < kTransUnroll; ++s) {
+      sr = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s].x, b[s].x, sr, 0, 0, 0);
+      si = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s].x, b[s].y, si, 0, 0, 0);
+      sr = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s].y, b[s].y, sr, 0, 0, 0);
+      si = __builtin_amdgcn_mfma_f64_16x16x4f64(-a[s].y, b[s].x, si, 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    red[wave][q][lane] = sr[q];
+    red[wave][4 + q][lane] = si[q];
+  }
+  __syncthreads();
+  const int e = threadIdx.x, jp = e >> 4, src = ((jp & 3) << 4) | (e & 15), reg = jp >> 2;
+  double x = 0.0, y = 0.0;
+  for (int w = 0; w < kThreads / 64; ++w) {
+    x += red[w][reg][src];
+    y += red[w][4 + reg][src];
+  }
+  part[((size_t)p * gridDim.x + blockIdx.x) * 256 + e] = aqc::cmk(x, y);
+}
+
+// out[p][e] = sum_s part[p][s][e], s ascending (a workgroup of 256 per pair)
+__global__ void k_dm_pair_transitions_sum(const cplx* __restrict__ part, int split, cplx* __restrict__ out) {
+  const int p = blockIdx.x;
+  double x = 0.0, y = 0.0;
+  for (int s = 0; s < split; ++s) {
+    const cplx v = part[((size_t)p * split + s) * 256 + threadIdx.x];
+    x += v.x;
+    y += v.y;
+  }
+  out[(size_t)p * 256 + threadIdx.x] = aqc::cmk(x, y);
 }
 
 // ---- host planning -----------------------------------------------------------------------------------
@@ -1187,6 +1285,49 @@ int aqc_dm_pair_envs(aqc_dm_t h, const int* pairs, int npairs, const double* eff
   }
   AQC_HIP_CHECK(hipMemcpyAsync(out, d_out, (size_t)npairs * 16 * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
   AQC_HIP_CHECK(hipStreamSynchronize(h->stream));  // (pairs and eff are read by the copies until here)
+  return AQC_OK;
+}
+
+int aqc_dm_pair_transitions_plan(int n, int npairs, int* split) {
+  AQC_REQUIRE(split != nullptr, "aqc_dm_pair_transitions_plan: null split");
+  AQC_REQUIRE(n >= 2 && n <= kMaxQubits, "aqc_dm_pair_transitions_plan: n must be in 2 .. 13");
+  AQC_REQUIRE(npairs >= 1 && npairs <= kMaxPairs, "aqc_dm_pair_transitions_plan: npairs must be in 1 .. 4096");
+  *split = trans_split(n, npairs);
+  return AQC_OK;
+}
+
+int aqc_dm_pair_transitions(aqc_dm_t a, aqc_dm_t b, const int* pairs, int npairs, double* out) {
+  AQC_REQUIRE(a && b && pairs && out && npairs >= 0 && npairs <= kMaxPairs, "aqc_dm_pair_transitions: bad arguments");
+  AQC_REQUIRE(a->n == b->n, "aqc_dm_pair_transitions: the two matrices have different qubit counts");
+  AQC_REQUIRE(a->n >= 2, "aqc_dm_pair_transitions: needs at least 2 qubits");
+  const int n = a->n;
+  for (int p = 0; p < npairs; ++p) {
+    const int x = pairs[2 * p], y = pairs[2 * p + 1];
+    AQC_REQUIRE(x >= 0 && x < n && y >= 0 && y < n && x != y, "aqc_dm_pair_transitions: bad pair");
+  }
+  if (npairs == 0) return AQC_OK;
+  const int split = trans_split(n, npairs);
+  const size_t pb = aqc::up256((size_t)2 * npairs * sizeof(int)), ob = (size_t)npairs * 256 * sizeof(cplx);
+  const size_t qb = split > 1 ? (size_t)npairs * split * 256 * sizeof(cplx) : 0;
+  char* buf = nullptr;
+  if (int rc = dm_buf(a, pb + ob + qb, &buf)) return rc;
+  cplx* d_out = (cplx*)(buf + pb);
+  cplx* d_part = split > 1 ? (cplx*)(buf + pb + ob) : d_out;
+  AQC_HIP_CHECK(hipMemcpyAsync(buf, pairs, (size_t)2 * npairs * sizeof(int), hipMemcpyHostToDevice, a->stream));
+  // a pair reads both matrices once (2 x 16 x 4^n bytes) for 256 complex MACs per value of o
+  const double items = (double)npairs * std::ldexp(1.0, 2 * n - 4);
+  aqc::KernelTimer::begin(a->stream, "dm_pair_transitions", 512.0 * items, 2048.0 * items);
+  hipLaunchKernelGGL(k_dm_pair_transitions, dim3(split, npairs), dim3(kThreads), 0, a->stream, a->rho, b->rho, n,
+                     (const int*)buf, d_part);
+  aqc::KernelTimer::end(a->stream);
+  AQC_CHECK_LAUNCH();
+  if (split > 1) {
+    hipLaunchKernelGGL(k_dm_pair_transitions_sum, dim3(npairs), dim3(256), 0, a->stream, (const cplx*)d_part, split,
+                       d_out);
+    AQC_CHECK_LAUNCH();
+  }
+  AQC_HIP_CHECK(hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, a->stream));
+  AQC_HIP_CHECK(hipStreamSynchronize(a->stream));  // (pairs is read by the copy until here)
   return AQC_OK;
 }
 

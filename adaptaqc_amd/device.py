@@ -268,6 +268,27 @@ class DeviceDM:
             _lib.check(self._l.aqc_dm_pair_envs(self.h, _lib.ptr(pairs), len(pairs) // 2, _lib.ptr(eff), _lib.ptr(out)))
         return out.reshape(-1, 4, 4)
 
+    def pair_transitions(self, ket, pairs):
+        """complex [npairs, 16, 16]: ``transition`` for pairs (aqc_dm_pair_transitions), T[j', j] =
+        sum_o conj(self[j', o]) ket[j, o] at the pair's local index j = (r_lo + 2 r_hi) + 4 (c_lo + 2 c_hi) --
+        ``noise.layer_superoperator``'s index, lo / hi the pair's smaller / larger qubit in whatever order it
+        is listed.  For a two-qubit superoperator S on the pair, Tr(self^H (S (x) id)(ket)) = sum(S * T): with
+        self a cost observable pulled back through everything behind a candidate layer and ``ket`` the state
+        in front of it, one call prices every candidate on every pair.  Fixed summation order."""
+        pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1))
+        out = np.zeros(len(pairs) // 2 * 256, dtype=np.complex128)
+        if len(pairs):
+            _lib.check(self._l.aqc_dm_pair_transitions(self.h, ket.h, _lib.ptr(pairs), len(pairs) // 2, _lib.ptr(out)))
+        return out.reshape(-1, 16, 16)
+
+
+def dm_pair_transitions_split(n, npairs=1):
+    """The workgroups ``DeviceDM.pair_transitions`` spreads one pair over, for ``npairs`` pairs of ``n``
+    qubits (aqc_dm_pair_transitions_plan; no GPU)."""
+    split = ctypes.c_int()
+    _lib.check(_lib.load().aqc_dm_pair_transitions_plan(int(n), int(npairs), ctypes.byref(split)))
+    return int(split.value)
+
 
 DM_PLAN_COUNTS = ("segments", "steps", "rows", "tile_bits")
 

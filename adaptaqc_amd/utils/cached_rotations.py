@@ -309,6 +309,35 @@ class SVPrefixBatch(_SweepBase):
         return [float(0.5 * (1 - np.mean(st.z_all()))) for st in self.cand[:len(mats)]]
 
 
+def noisy_rows(circuit, lo, hi, noise_model, measures=False):
+    """The program of ``circuit.data[lo:hi]`` (its measures dropped) under ``noise_model``; with ``measures``
+    (the piece a backward pass starts with) followed by the errors of one terminal measure per qubit, as
+    ``DensityMatrixBackend``'s program ends."""
+    from ..noise import kraus_row, trajectory_program
+
+    view = _View(circuit, lo, hi)
+    view.data = [ins for ins in view.data if ins.operation.name != "measure"]
+    rows = trajectory_program(view, noise_model)[0]
+    if measures and noise_model is not None:
+        tail = [kraus_row(e, q) for k in range(circuit.num_qubits) for q, e in noise_model.channels("measure", (k,))]
+        if tail:
+            rows = np.concatenate([rows] + tail)
+    return rows
+
+
+def load_cost_observable(dev, kind):
+    """``dev`` <- O of a cost Tr(O rho_final) / Tr rho: |0...0><0...0| ("global": the cost is 1 minus it) or
+    diag(popcount(k) / n) ("local")."""
+    if kind == "global":
+        dev.reset()
+    elif kind == "local":
+        k = np.arange(2 ** dev.n, dtype=np.uint64)
+        pop = sum(((k >> np.uint64(b)) & np.uint64(1)).astype(np.float64) for b in range(dev.n))
+        dev.set_diag(pop / dev.n)
+    else:
+        raise ValueError("load_cost_observable: the global or the local cost")
+
+
 class DMHeisenbergSweep(_SweepBase):
     """Density matrix, global or local cost under a noise model: every candidate of a gate from one 4x4
     transition matrix.
@@ -358,31 +387,13 @@ class DMHeisenbergSweep(_SweepBase):
         return self._own[:count]
 
     def _rows(self, lo, hi, measures=False):
-        """The program of ``data[lo:hi]`` under the noise model; with ``measures`` (the piece a backward
-        pass starts with) followed by the errors of one terminal measure per qubit, as the backend's
-        program ends."""
-        from ..noise import kraus_row, trajectory_program
-
-        circ = self.compiler.full_circuit
-        view = _View(circ, lo, hi)
-        view.data = [ins for ins in view.data if ins.operation.name != "measure"]
-        rows = trajectory_program(view, self.noise_model)[0]
-        if measures and self.noise_model is not None:
-            tail = [kraus_row(e, q) for k in range(self.n) for q, e in self.noise_model.channels("measure", (k,))]
-            if tail:
-                rows = np.concatenate([rows] + tail)
-        return rows
+        return noisy_rows(self.compiler.full_circuit, lo, hi, self.noise_model, measures)
 
     def _checkpoint(self, first):
         """One backward pass: M at cycle[first], ... for as many positions as there are checkpoints."""
         positions = self.cycle[first:first + self.capacity]
         slots = self._states(2 + len(positions))[2:]
-        if self.kind == "global":
-            self.obs.reset()
-        else:
-            k = np.arange(2 ** self.n, dtype=np.uint64)
-            pop = sum(((k >> np.uint64(b)) & np.uint64(1)).astype(np.float64) for b in range(self.n))
-            self.obs.set_diag(pop / self.n)
+        load_cost_observable(self.obs, self.kind)
         self.where = {}
         hi, measures = len(self.compiler.full_circuit.data), True
         for slot, p in zip(reversed(slots), reversed(positions)):

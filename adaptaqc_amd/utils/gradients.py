@@ -238,26 +238,15 @@ def shifted_layers(layer: QuantumCircuit, rotoselect: bool, shift: float):
     return out
 
 
-def noisy_grads_from_envs(envs, trace, effects, layer, coupling_map, noise_model, rotoselect):
-    """The noise-aware general gradient of every ordered pair (c, t) of ``coupling_map`` from the pairs'
-    environments (host only).
-
-    ``envs``: complex [len(coupling_map), 4, 4], R of each pair at the index 2 bit_hi + bit_lo
-    (``DeviceDM.pair_envs``; not divided by the trace); ``trace``: Tr rho; ``effects``: [n, 4] as
-    ``noise.terminal_effects``.  With S the superoperator of a candidate circuit on (c, t) under
-    ``noise_model`` (``noise.layer_superoperator``), C = 1 - Re Tr((E_hi (x) E_lo) S(R)) / Tr rho, and
-    g_{i,op} = [C(L_{i,op}(+pi/2)) - C(L_{i,op}(-pi/2))] / 2 is dC/dtheta at 0 exactly (C is a + b cos theta +
-    c sin theta in one rotation angle whatever fixed channels follow).  Returns sqrt(sum_{i,op} g^2) per
-    pair; with ``noise_model`` None that is the reference's sqrt(sum_k deg_k g_k^2)."""
+def _shifted_half_differences(layer, noise_model, rotoselect):
+    """half(c, t) -> complex [candidates, 16, 16]: [S(L_{i,op}(+pi/2)) - S(L_{i,op}(-pi/2))] / 2 of every shifted
+    candidate of ``layer`` on the ordered pair (c, t) under ``noise_model`` (``noise.layer_superoperator``'s
+    index), in ``shifted_layers``'s order; what the noise-aware gradients of every kind share.  Without errors
+    attached to particular qubits the maps depend on the pair's orientation alone and are made once each."""
     from ..noise import layer_superoperator
 
-    envs = np.asarray(envs, dtype=complex).reshape(-1, 4, 4)
-    effects = np.asarray(effects, dtype=float)
-    if len(envs) != len(coupling_map):
-        raise ValueError("noisy_grads_from_envs: one environment per pair of the coupling map")
     plus = shifted_layers(layer, rotoselect, np.pi / 2)
     minus = shifted_layers(layer, rotoselect, -np.pi / 2)
-    # without errors attached to particular qubits the maps depend on the pair's orientation alone
     local = noise_model is not None and bool(getattr(noise_model, "_local", None))
     cache = {}
 
@@ -269,17 +258,66 @@ def noisy_grads_from_envs(envs, trace, effects, layer, coupling_map, noise_model
                                    for p, m in zip(plus, minus)]) if plus else np.zeros((0, 16, 16), dtype=complex)
         return cache[key]
 
+    return half_differences
+
+
+def _pair_gradient_norms(coupling_map, per_pair, value_of):
+    """sqrt(sum_{i,op} g^2) per ordered pair: ``value_of((c, t), the pair's entry of per_pair)`` gives the
+    g_{i,op} of one pair."""
+    out = []
+    for (c, t), data in zip(coupling_map, per_pair):
+        g = value_of((int(c), int(t)), data)
+        out.append(float(np.sqrt(np.sum(g * g))))
+    return out
+
+
+def noisy_grads_from_envs(envs, trace, effects, layer, coupling_map, noise_model, rotoselect):
+    """The noise-aware general gradient of every ordered pair (c, t) of ``coupling_map`` from the pairs'
+    environments (host only).
+
+    ``envs``: complex [len(coupling_map), 4, 4], R of each pair at the index 2 bit_hi + bit_lo
+    (``DeviceDM.pair_envs``; not divided by the trace); ``trace``: Tr rho; ``effects``: [n, 4] as
+    ``noise.terminal_effects``.  With S the superoperator of a candidate circuit on (c, t) under
+    ``noise_model`` (``noise.layer_superoperator``), C = 1 - Re Tr((E_hi (x) E_lo) S(R)) / Tr rho, and
+    g_{i,op} = [C(L_{i,op}(+pi/2)) - C(L_{i,op}(-pi/2))] / 2 is dC/dtheta at 0 exactly (C is a + b cos theta +
+    c sin theta in one rotation angle whatever fixed channels follow).  Returns sqrt(sum_{i,op} g^2) per
+    pair; with ``noise_model`` None that is the reference's sqrt(sum_k deg_k g_k^2)."""
+    envs = np.asarray(envs, dtype=complex).reshape(-1, 4, 4)
+    effects = np.asarray(effects, dtype=float)
+    if len(envs) != len(coupling_map):
+        raise ValueError("noisy_grads_from_envs: one environment per pair of the coupling map")
+    half_differences = _shifted_half_differences(layer, noise_model, rotoselect)
+
     def matrix(e):
         return np.array([[e[0], e[2] + 1j * e[3]], [e[2] - 1j * e[3], e[1]]])
 
-    out = []
-    for (c, t), env in zip(coupling_map, envs):
-        c, t = int(c), int(t)
-        lo, hi = min(c, t), max(c, t)
+    def value_of(pair, env):
+        lo, hi = min(pair), max(pair)
         evec = np.kron(matrix(effects[hi]), matrix(effects[lo])).reshape(-1)  # Tr(E X) = evec . vec(X)
-        g = -np.real(half_differences(c, t) @ env.reshape(-1, order="F") @ evec) / trace
-        out.append(float(np.sqrt(np.sum(g * g))))
-    return out
+        return -np.real(half_differences(*pair) @ env.reshape(-1, order="F") @ evec) / trace
+
+    return _pair_gradient_norms(coupling_map, envs, value_of)
+
+
+def noisy_grads_from_transitions(trans, trace, layer, coupling_map, noise_model, rotoselect, sign):
+    """``noisy_grads_from_envs``'s gradients from the pairs' transition matrices (host only): for any
+    right-hand side and either cost.
+
+    ``trans``: complex [len(coupling_map), 16, 16], T of each pair between the cost observable pulled back
+    through everything behind the layer and the state in front of it (``DeviceDM.pair_transitions``); ``trace``:
+    Tr rho.  A candidate circuit on (c, t) with superoperator S costs C = ``sign`` Re sum(S * T) / Tr rho plus a
+    constant: ``sign`` -1 for the global cost (1 minus that value), +1 for the local cost (the value itself).
+    g_{i,op} = [C(L_{i,op}(+pi/2)) - C(L_{i,op}(-pi/2))] / 2, sqrt(sum_{i,op} g^2) per pair, as
+    ``noisy_grads_from_envs``."""
+    trans = np.asarray(trans, dtype=complex).reshape(-1, 16, 16)
+    if len(trans) != len(coupling_map):
+        raise ValueError("noisy_grads_from_transitions: one transition matrix per pair of the coupling map")
+    half_differences = _shifted_half_differences(layer, noise_model, rotoselect)
+
+    def value_of(pair, t):
+        return float(sign) * np.real(np.sum(half_differences(*pair) * t, axis=(1, 2))) / trace
+
+    return _pair_gradient_norms(coupling_map, trans, value_of)
 
 
 def noisy_general_grad_of_pairs(compiler):
@@ -299,10 +337,28 @@ def noisy_general_grad_of_pairs(compiler):
                                  compiler.use_rotoselect)
 
 
+def noisy_transition_grad_of_pairs(compiler, cost="global"):
+    """``noisy_general_grad_of_pairs`` for any right-hand side and either cost, on a ``DensityMatrixBackend``:
+    one ``DeviceDM.pair_transitions`` call over the unordered pairs (``pair_transition_matrices``) and host
+    arithmetic per candidate (``noisy_grads_from_transitions``)."""
+    cmap = [(int(c), int(t)) for c, t in compiler.coupling_map]
+    if not cmap:
+        return []
+    unordered = sorted({(min(c, t), max(c, t)) for c, t in cmap})
+    trans, trace = compiler.backend.pair_transition_matrices(compiler, unordered, cost)
+    where = {p: k for k, p in enumerate(unordered)}
+    trans = np.stack([trans[where[(min(c, t), max(c, t))]] for c, t in cmap])
+    noise_model = (getattr(compiler, "execute_kwargs", None) or {}).get("noise_model")
+    return noisy_grads_from_transitions(trans, trace, compiler.layer_2q_gate, cmap, noise_model,
+                                        compiler.use_rotoselect, -1.0 if cost == "global" else 1.0)
+
+
 __all__ = [
     "general_grad_of_pairs",
     "noisy_grads_from_envs",
+    "noisy_grads_from_transitions",
     "noisy_general_grad_of_pairs",
+    "noisy_transition_grad_of_pairs",
     "get_generators_and_degeneracies",
     "get_generator",
     "circuit_unitary",

@@ -481,6 +481,24 @@ int aqc_dm_pair_rdms(aqc_dm_t h, const int* pairs, int npairs, double* out);
    calls give the same bits.  rho is any matrix (aqc_dm_set) and is not changed.  n >= 2, at most 4096
    pairs; AQC_ERR_ARG also for an effect that is not finite. */
 int aqc_dm_pair_envs(aqc_dm_t h, const int* pairs, int npairs, const double* effects, double* out);
+/* aqc_dm_transition for pairs.  out[p] = T, 16x16 complex, row-major (j' major) as (re, im):
+     T[j', j] = sum_o conj(A[j', o]) B[j, o],   j = (r_lo + 2 r_hi) + 4 (c_lo + 2 c_hi),
+   lo / hi the smaller / larger qubit of pair p in whatever order it is listed (index bits lo, hi, n + lo,
+   n + hi of the entry), o the other 2n - 4 index bits.  For any two-qubit superoperator S at that index (an
+   aqc_dm_plan step on (lo, hi)), Tr(A^H (S (x) id)(B)) = sum_{j', j} S[j', j] T[j', j]: with A a cost observable
+   pulled back through everything behind a candidate layer (aqc_dm_apply_adjoint) and B the state in front of
+   it, every candidate layer on the pair is priced on the host, whatever follows it.  Summing T over the
+   partner's equal indices gives aqc_dm_transition's T of either qubit.
+   Per pair a 16 x 16 x 4^(n-2) complex product on the FP64 matrix cores; both matrices are read once per
+   pair.  A pair is spread over aqc_dm_pair_transitions_plan's workgroups, each adding its waves' tiles in order,
+   and a second pass adds a pair's workgroups in order: no atomics, two calls give the same bits.  a == b is
+   allowed; neither is changed.  AQC_ERR_ARG: different qubit counts, n < 2, a qubit out of range, a pair of
+   equal qubits, more than 4096 pairs. */
+int aqc_dm_pair_transitions(aqc_dm_t a, aqc_dm_t b, const int* pairs, int npairs, double* out);
+/* Host only (no GPU): *split = the workgroups aqc_dm_pair_transitions spreads one pair over for npairs pairs
+   of n qubits: 1 while 4^(n-2) <= 256, then 256 values of o a workgroup up to 256 workgroups (4 at n = 7),
+   halved while split x npairs exceeds 8192.  AQC_ERR_ARG: n outside 2 .. 13, npairs outside 1 .. 4096. */
+int aqc_dm_pair_transitions_plan(int n, int npairs, int* split);
 
 /* ---- Pauli-string expectation values: replaces circuit_operations_pauli_ops.py:60-100 -------------
    (expectation_value_of_pauli_operator, which runs one rotated circuit per term).
