@@ -55,6 +55,7 @@ EXPORTS = (
     "aqc_mps_traj_set_correlated",
     "aqc_mps_traj_pair_tomo", "aqc_mps_traj_tomo_plan", "aqc_mps_traj_set_readout_batch", "aqc_mps_traj_pauli_counts",
     "aqc_sv_pauli_expect", "aqc_mps_pauli_expect", "aqc_mps_pauli_expect_batch",
+    "aqc_sv_pauli_apply", "aqc_sv_dot", "aqc_sv_axpby",
     "aqc_pair_tomo_probs", "aqc_concurrence_bound_probs", "aqc_multinomial_counts", "aqc_tomo_fit",
     "aqc_dm_create", "aqc_dm_destroy", "aqc_dm_reset", "aqc_dm_apply", "aqc_dm_plan", "aqc_dm_get", "aqc_dm_trace0",
     "aqc_dm_diag_sv", "aqc_dm_pauli_expect", "aqc_dm_pair_rdms",
@@ -181,6 +182,9 @@ _SIGS = {
     "aqc_mps_traj_pauli_counts": ([_I, _I, _D, _I, _P, _I, _P, _I, _P, _I, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P, _P,
                                    _P], _I),
     "aqc_sv_pauli_expect": ([_P, _P, _P, _I, _P], _I),
+    "aqc_sv_pauli_apply": ([_P, _P, _P, _P, _P, _I], _I),
+    "aqc_sv_dot": ([_P, _P, _DP], _I),
+    "aqc_sv_axpby": ([_P, _D, _D, _P, _D, _D], _I),
     "aqc_mps_pauli_expect": ([_P, _P, _I, _P], _I),
     "aqc_mps_pauli_expect_batch": ([_P, _I, _P, _I, _P], _I),
     "aqc_pair_tomo_probs": ([_P, _I, _P, _I], _I),

@@ -165,6 +165,18 @@ __device__ __forceinline__ double group_sum(double v) {
   else return row_sum16(v);
 }
 
+// Sum over a workgroup of 256 threads in a fixed order (lane tree, then the four waves in order); the
+// result in thread 0.  red: four doubles of LDS, free again on return.
+__device__ __forceinline__ double block_sum256(double v, double* red) {
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = 0.0;
+  if (threadIdx.x == 0) s = ((red[0] + red[1]) + red[2]) + red[3];
+  __syncthreads();
+  return s;
+}
+
 // ---- teardown ----------------------------------------------------------------------------
 // Lazily created HIP objects (side streams, events, the memory pool) register a cleanup here
 // when they are first created; aqc_finalize synchronises every device the library touched, runs
@@ -251,6 +263,10 @@ int sv_view(aqc_sv_t h, const cplx** state, int* n, hipStream_t* stream);
 // The n-qubit statevector handle for a caller that overwrites every amplitude (dm.hip's diagonal): a
 // deferred reset is dropped, not materialised.  AQC_ERR_ARG, and the handle untouched, for another n.
 int sv_overwrite(aqc_sv_t h, int n, cplx** state, hipStream_t* stream);
+// The handle for a caller that updates the amplitudes in place (sv_linalg.hip): a deferred reset is
+// materialised first.
+int sv_mutable(aqc_sv_t h, cplx** state, int* n, hipStream_t* stream);
+int sv_qubits(aqc_sv_t h);
 
 // ---- kernel timing (HIP events on the launching stream) ------------------------------
 struct KernelTimer {

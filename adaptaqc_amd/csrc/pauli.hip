@@ -44,15 +44,7 @@ constexpr int kMaxWg = 2048;                    // and of its grid (8 workgroups
 constexpr int kMaxTermsPerLaunch = 32768;       // gridDim.y of the statevector kernel
 
 // sum over the block in a fixed order (lane tree, then the four waves in order); the result in thread 0
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  if (threadIdx.x == 0) s = ((red[0] + red[1]) + red[2]) + red[3];
-  __syncthreads();
-  return s;
-}
+__device__ __forceinline__ double block_sum(double v, double* red) { return aqc::block_sum256(v, red); }
 
 // ---- statevector -------------------------------------------------------------------------------
 // blockIdx.y: term, blockIdx.x: block of the term; partial[term * gridDim.x + blockIdx.x]

@@ -930,6 +930,17 @@ int aqc::sv_overwrite(aqc_sv_t h, int n, cplx** state, hipStream_t* stream) {
   return AQC_OK;
 }
 
+int aqc::sv_mutable(aqc_sv_t h, cplx** state, int* n, hipStream_t* stream) {
+  if (int rc = sv_materialize(h)) return rc;
+  h->amp0_ready = false;
+  *state = h->state;
+  *n = h->n;
+  *stream = h->stream;
+  return AQC_OK;
+}
+
+int aqc::sv_qubits(aqc_sv_t h) { return h->n; }
+
 static int sv_scratch(aqc_sv_t h, size_t bytes, char** out) {
   if (bytes > h->scratch_cap) {
     AQC_HIP_CHECK(hipStreamSynchronize(h->stream));

@@ -87,6 +87,37 @@ class DeviceSV:
         _lib.check(self._l.aqc_sv_pauli_expect(self.h, _lib.ptr(x), _lib.ptr(z), len(x), _lib.ptr(out)))
         return out
 
+    def pauli_apply(self, operator, out):
+        """out <- sum_t c_t P_t self (aqc_sv_pauli_apply); self is not changed.  ``operator``: a
+        ``{label: coefficient}`` dict (qiskit labels, rightmost character = qubit 0) or ``(terms,
+        coeffs)`` with terms as ``pauli_expect`` takes them.  ``out``: another DeviceSV on as many qubits."""
+        from . import paulis
+
+        x, z, c = paulis.operator_to_masks(operator, self.n)
+        return self.pauli_apply_masks(x, z, c, out)
+
+    def pauli_apply_masks(self, xmask, zmask, coeffs, out):
+        """The same from bit masks and complex coefficients."""
+        x = np.ascontiguousarray(xmask, dtype=np.uint64).reshape(-1)
+        z = np.ascontiguousarray(zmask, dtype=np.uint64).reshape(-1)
+        c = np.ascontiguousarray(coeffs, dtype=np.complex128).reshape(-1)
+        if not len(x) == len(z) == len(c):
+            raise ValueError("pauli_apply_masks: one x mask, z mask and coefficient per term")
+        _lib.check(self._l.aqc_sv_pauli_apply(self.h, out.h if out is not None else None, _lib.ptr(x), _lib.ptr(z),
+                                              _lib.ptr(c), len(x)))
+        return out
+
+    def dot(self, other):
+        """<self|other> = sum_k conj(self_k) other_k, summed in a fixed order (aqc_sv_dot)."""
+        out = np.zeros(2)
+        _lib.check(self._l.aqc_sv_dot(self.h, other.h if other is not None else None, _lib.dptr(out)))
+        return complex(out[0], out[1])
+
+    def axpby(self, a, x=None, b=0.0):
+        """self <- a self + b x (aqc_sv_axpby); with b = 0, x may be None: a pure scale."""
+        a, b = complex(a), complex(b)
+        _lib.check(self._l.aqc_sv_axpby(self.h, a.real, a.imag, x.h if x is not None else None, b.real, b.imag))
+
     def get(self):
         out = np.zeros(2 ** self.n, dtype=np.complex128)
         _lib.check(self._l.aqc_sv_get(self.h, _lib.ptr(out)))

@@ -391,3 +391,40 @@ def mps_to_vector(mps, already_preprocessed=False):
     """Dense statevector of a (small) MPS, evaluated amplitude by amplitude on the device."""
     d = _as_device(mps, already_preprocessed)
     return np.array([extract_amplitude(d, i) for i in range(2 ** d.n)])
+
+
+def mps_from_vector(psi, trunc_thr=1e-16, max_chi=None):
+    """Aer-format MPS ``(gam, lam)`` of a dense statevector (index bit q = qubit q; site q = qubit q,
+    the convention ``mps_to_vector`` inverts), by successive SVDs on the host.  A format conversion
+    at the ingestion boundary, like ``DeviceMPS.load_aer``: it runs once, to make a state such as
+    ``calculate_ground_state``'s a compile target, and sits on no evaluation path.
+
+    Vidal form, psi = Gamma_0 lam_0 Gamma_1 ... lam_{n-2} Gamma_{n-1}: every bond's lambdas descend,
+    those with lambda^2 <= ``trunc_thr`` are dropped (the largest is always kept) and at most
+    ``max_chi`` are kept.  The kept lambdas are not rescaled: a truncated result has the norm of what
+    was kept."""
+    psi = np.asarray(psi, dtype=np.complex128).reshape(-1)
+    n = int(psi.size).bit_length() - 1
+    if n < 1 or psi.size != 1 << n:
+        raise ValueError(f"mps_from_vector: the vector needs 2^n entries with n >= 1, got {psi.size}")
+    if max_chi is not None and int(max_chi) < 1:
+        raise ValueError("mps_from_vector: max_chi must be at least 1")
+    # axis q of the tensor = qubit q (the dense index has qubit n-1 as its slowest bit)
+    rest = psi.reshape((2,) * n).transpose(tuple(range(n - 1, -1, -1))).reshape(1, -1)
+    gam, lam = [], []
+    prev = np.ones(1)
+    for _ in range(n - 1):
+        chi_l = rest.shape[0]
+        u, s, vh = np.linalg.svd(rest.reshape(chi_l * 2, -1), full_matrices=False)
+        keep = max(1, int(np.count_nonzero(s * s > trunc_thr)))
+        if max_chi is not None:
+            keep = min(keep, int(max_chi))
+        u, s, vh = u[:, :keep], s[:keep], vh[:keep]
+        g = u.reshape(chi_l, 2, keep) / prev[:, None, None]
+        gam.append((np.ascontiguousarray(g[:, 0, :]), np.ascontiguousarray(g[:, 1, :])))
+        lam.append(s.copy())
+        rest = s[:, None] * vh
+        prev = s
+    g = rest.reshape(rest.shape[0], 2, 1) / prev[:, None, None]
+    gam.append((np.ascontiguousarray(g[:, 0, :]), np.ascontiguousarray(g[:, 1, :])))
+    return gam, lam

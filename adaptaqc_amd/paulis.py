@@ -67,6 +67,43 @@ def label_to_masks(label, n=None):
     return int(x[0]), int(z[0])
 
 
+def operator_to_masks(operator, n):
+    """(xmask, zmask, coeffs) of a Pauli sum on n qubits: a ``{label: coefficient}`` dict, or
+    ``(terms, coeffs)`` with terms as ``terms_to_codes`` takes them.  coeffs: complex128[nterms]."""
+    if isinstance(operator, dict):
+        terms, coeffs = list(operator.keys()), list(operator.values())
+    else:
+        terms, coeffs = operator
+    x, z = codes_to_masks(terms_to_codes(terms, n))
+    coeffs = np.ascontiguousarray(np.asarray(coeffs, dtype=np.complex128).reshape(-1))
+    if len(coeffs) != len(x):
+        raise ValueError(f"a Pauli sum needs one coefficient per term: {len(x)} terms, {len(coeffs)} coefficients")
+    return x, z, coeffs
+
+
+def group_by_xmask(xmask, zmask, coeffs):
+    """The grouping aqc_sv_pauli_apply does on the host, restated: with P = i^popcount(x & z) X^x Z^z,
+    (sum_t c_t P_t psi)[j] = sum_g psi[j ^ X_g] sum_{t in g} c'_t (-1)^popcount((j ^ X_g) & z_t),
+    c'_t = i^popcount(x_t & z_t) c_t.  Returns a list of ``(X_g, [(z_t, c'_t), ...])``: groups in order
+    of first appearance of their x mask, terms of a group in input order (the order the kernel sums
+    in).  The phase is applied by exchanging and negating the parts, so c' holds the bits of c."""
+    xmask = [int(v) for v in np.asarray(xmask).reshape(-1)]
+    zmask = [int(v) for v in np.asarray(zmask).reshape(-1)]
+    coeffs = [complex(c) for c in np.asarray(coeffs).reshape(-1)]
+    if not len(xmask) == len(zmask) == len(coeffs):
+        raise ValueError("group_by_xmask: one x mask, z mask and coefficient per term")
+    index = {}
+    groups = []
+    for x, z, c in zip(xmask, zmask, coeffs):
+        ny = bin(x & z).count("1") & 3
+        cp = (c, complex(-c.imag, c.real), -c, complex(c.imag, -c.real))[ny]
+        if x not in index:
+            index[x] = len(groups)
+            groups.append((x, []))
+        groups[index[x]][1].append((z, cp))
+    return groups
+
+
 def parity_from_counts(counts, qubits):
     """Average of (-1)^(number of ones among ``qubits``) over a counts dict; keys are qiskit
     bitstrings, read right to left (qubit q is character -1 - q).  Spaces (register separators)

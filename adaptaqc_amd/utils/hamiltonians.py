@@ -19,7 +19,28 @@ The reference builds OpenFermion ``QubitOperator``s and converts them with
 coefficient}`` dict that ``expectation_value_of_pauli_operator`` takes directly (labels in qiskit
 order: the rightmost character is qubit 0).  The Anderson model (hamiltonians.py:42-77) needs
 OpenFermion's Jordan-Wigner transform and is not provided.
+
+``calculate_ground_state`` (hamiltonians.py:80-85, there OpenFermion's sparse eigensolver on the
+host) is a Lanczos iteration on device statevectors: the operator apply, the inner products and
+the vector updates are libaqchip kernels (csrc/sv_linalg.hip); the host holds the tridiagonal.
 """
+import math
+from dataclasses import dataclass
+
+import numpy as np
+
+
+@dataclass
+class GroundStateRun:
+    """What the last ``calculate_ground_state`` call did (``last_run``)."""
+    energy: float       # <psi|H|psi> of the returned state
+    residual: float     # r = |H psi - E psi|, measured on the device
+    scale: float        # S = sum_t |c_t|; the call converged to r <= tol * S
+    iterations: int     # Lanczos steps (operator applies of the first passes), all restarts together
+    restarts: int       # restarts taken after the first run
+
+
+last_run = None
 
 
 def _label(n, ops):
@@ -52,3 +73,123 @@ def heisenberg_hamiltonian(n=4, jx=1.0, jy=0.0, jz=0.0, hx=0.0, hy=0.0, hz=0.0, 
         for p, c in (("X", hx), ("Y", hy), ("Z", hz)):
             add(_label(n, [(i, p)]), -c)
     return ham
+
+
+def _checked_hamiltonian(hamiltonian):
+    """(n, xmask, zmask, real coefficients as complex128, S) of a label dict, or ValueError."""
+    from .. import paulis
+
+    if not isinstance(hamiltonian, dict) or len(hamiltonian) == 0:
+        raise ValueError("calculate_ground_state: the Hamiltonian must be a non-empty {label: coefficient} dict")
+    labels = list(hamiltonian.keys())
+    n = len(labels[0]) if isinstance(labels[0], str) else 0
+    if n < 1 or any(not isinstance(s, str) or len(s) != n for s in labels):
+        raise ValueError("calculate_ground_state: every label must be a string of the same length (one letter a qubit)")
+    coeffs = np.asarray([complex(v) for v in hamiltonian.values()], dtype=np.complex128)
+    if not np.all(np.isfinite(coeffs.real)) or not np.all(np.isfinite(coeffs.imag)):
+        raise ValueError("calculate_ground_state: a coefficient is not finite")
+    if np.any(coeffs.imag != 0):
+        bad = labels[int(np.flatnonzero(coeffs.imag != 0)[0])]
+        raise ValueError(f"calculate_ground_state: the coefficient of {bad!r} has an imaginary part; a Hamiltonian "
+                         f"(a Hermitian Pauli sum) has real coefficients")
+    x, z, c = paulis.operator_to_masks((labels, coeffs), n)
+    return n, x, z, c, float(np.sum(np.abs(coeffs)))
+
+
+def _lowest_ritz(alphas, betas):
+    """Lowest eigenpair (theta, s) of the symmetric tridiagonal with diagonal alphas, off-diagonal betas."""
+    if len(alphas) == 1:
+        return float(alphas[0]), np.ones(1)
+    from scipy.linalg import eigh_tridiagonal
+
+    w, v = eigh_tridiagonal(np.asarray(alphas), np.asarray(betas), select="i", select_range=(0, 0),
+                            lapack_driver="stemr")
+    return float(w[0]), v[:, 0]
+
+
+def calculate_ground_state(hamiltonian, tol=1e-9, max_iterations=300, max_restarts=5, seed=0, return_device=False):
+    """hamiltonians.py:80-85: ``(gs_energy, gs_wf)`` of a Hamiltonian, here the ``{label: real
+    coefficient}`` dict ``heisenberg_hamiltonian`` returns (the reference takes a QubitOperator).
+
+    ``gs_wf`` is a normalised complex128 array of 2^n amplitudes whose index bit q is qubit q, this
+    package's convention everywhere.  The reference's vector comes from OpenFermion's sparse operator,
+    where qubit 0 is the MOST significant bit of the index: reverse the bits of the index to compare.
+    With ``return_device`` the state is returned as the ``DeviceSV`` that holds it.
+
+    Lanczos with the three-term recurrence on device vectors, no stored basis.  The start vector is a
+    complex Gaussian vector fixed by ``seed`` (complex, so that it has weight in every symmetry sector
+    of a real Hamiltonian).  After each step the lowest Ritz pair (theta, s) of the tridiagonal is solved
+    on the host, and the run stops at |beta_m s_m| <= tol S, S = sum_t |c_t|, or after ``max_iterations``
+    steps.  The Ritz vector is formed by running the recurrence a second time from the same start
+    vector (the kernels sum in a fixed order, so the vectors repeat bit for bit).  Then the residual
+    r = |H psi - E psi| is measured on the device; while r > tol S the iteration restarts from psi, at most
+    ``max_restarts`` times -- this is what answers the recurrence's loss of orthogonality.
+
+    The returned state has r <= tol S, or the call raises ``RuntimeError`` naming r: an unconverged state is
+    never returned.  At a degenerate ground level the state is some vector of the ground space.
+    ``last_run`` keeps r, the steps and the restarts of the last call.  Four state-sized device buffers."""
+    global last_run
+    n, x, z, c, scale = _checked_hamiltonian(hamiltonian)
+    tol, max_iterations, max_restarts = float(tol), int(max_iterations), int(max_restarts)
+    if not tol > 0 or max_iterations < 1 or max_restarts < 0:
+        raise ValueError("calculate_ground_state: tol > 0, max_iterations >= 1 and max_restarts >= 0")
+    from ..device import DeviceSV
+
+    dim = 1 << n
+    steps = min(max_iterations, dim)
+    psi, v_prev, v, w = (DeviceSV(n) for _ in range(4))
+    rng = np.random.default_rng(seed)
+    psi.set(rng.standard_normal(dim) + 1j * rng.standard_normal(dim))
+    psi.axpby(1.0 / math.sqrt(psi.dot(psi).real))
+    bound = tol * scale
+    iterations = 0
+    for restart in range(max_restarts + 1):
+        # first pass: alpha, beta and the Ritz pair; psi holds the start vector
+        v.copy_from(psi)
+        alphas, betas = [], []
+        while True:
+            j = len(alphas)
+            v.pauli_apply_masks(x, z, c, w)
+            alphas.append(v.dot(w).real)
+            w.axpby(1.0, v, -alphas[j])
+            if j > 0:
+                w.axpby(1.0, v_prev, -betas[j - 1])
+            beta = math.sqrt(max(w.dot(w).real, 0.0))
+            _, s = _lowest_ritz(alphas, betas)
+            if beta * abs(s[-1]) <= bound or j + 1 == steps:
+                break
+            betas.append(beta)
+            v_prev, v, w = v, w, v_prev
+            v.axpby(1.0 / beta)
+        iterations += len(alphas)
+        # second pass: the same vectors again, psi <- sum_j s_j v_j
+        v.copy_from(psi)
+        psi.axpby(s[0])
+        for j in range(len(alphas) - 1):
+            v.pauli_apply_masks(x, z, c, w)
+            w.axpby(1.0, v, -alphas[j])
+            if j > 0:
+                w.axpby(1.0, v_prev, -betas[j - 1])
+            v_prev, v, w = v, w, v_prev
+            v.axpby(1.0 / betas[j])
+            psi.axpby(1.0, v, s[j + 1])
+        psi.axpby(1.0 / math.sqrt(psi.dot(psi).real))
+        # the true residual
+        psi.pauli_apply_masks(x, z, c, w)
+        energy = psi.dot(w).real
+        w.axpby(1.0, psi, -energy)
+        residual = math.sqrt(max(w.dot(w).real, 0.0))
+        last_run = GroundStateRun(energy=energy, residual=residual, scale=scale, iterations=iterations, restarts=restart)
+        if residual <= bound:
+            break
+    for buf in (v_prev, v, w):
+        buf.close()
+    if not residual <= bound:
+        psi.close()
+        raise RuntimeError(f"calculate_ground_state: residual |H psi - E psi| = {residual:.3e} above tol * S = {bound:.3e} "
+                           f"after {iterations} Lanczos steps and {max_restarts} restarts")
+    if return_device:
+        return energy, psi
+    out = psi.get()
+    psi.close()
+    return energy, out

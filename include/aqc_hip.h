@@ -507,6 +507,26 @@ int aqc_dm_pair_transitions_plan(int n, int npairs, int* split);
    All terms go in one launch; sums run in a fixed order (no atomics): the same state gives the
    same bits. */
 int aqc_sv_pauli_expect(aqc_sv_t h, const uint64_t* xmask, const uint64_t* zmask, int nterms, double* out);
+/* ---- operator apply and vector operations: what a Krylov ground-state solver needs (replaces the
+   host eigensolver behind hamiltonians.py:80-85, calculate_ground_state) ---------------------------
+   out = sum_t c_t P_t in, P_t as above, c_t = coeff[2t] + i coeff[2t+1]:
+   out[j] = sum_t c_t i^{ny_t} (-1)^{popcount((j ^ x_t) & z_t)} in[j ^ x_t].  nterms == 0: out = 0.  An
+   all-identity term (x = z = 0) is an offset c in.  The terms are grouped by x mask (groups in order of
+   first appearance, terms of a group in input order); an amplitude is the sum over the groups in that
+   order of (sum of the group's +-c_t i^{ny_t} in term order) times in[j ^ X]; a group of more than 383
+   terms is cut into runs of 383 that are summed like groups.  No atomics: the same inputs give the
+   same bits.  in is not modified.
+   AQC_ERR_ARG, with out untouched: a null handle, in == out, different qubit counts, a mask bit at or
+   above n, a coefficient that is not finite, nterms outside 0 .. 2^20. */
+int aqc_sv_pauli_apply(aqc_sv_t in, aqc_sv_t out, const uint64_t* xmask, const uint64_t* zmask, const double* coeff,
+                       int nterms);
+/* out2 = (re, im) of sum_k conj(a_k) b_k, summed in a fixed order (a thread's terms in index order, the
+   wave, the waves in order, then the workgroups' partials in order).  a == b is allowed. */
+int aqc_sv_dot(aqc_sv_t a, aqc_sv_t b, double* out2);
+/* y <- (ar + i ai) y + (br + i bi) x.  b == 0: x is not read and may be NULL (a pure scale).
+   AQC_ERR_ARG: a null y, x == y, a null x with b != 0, different qubit counts, a coefficient that is not
+   finite. */
+int aqc_sv_axpby(aqc_sv_t y, double ar, double ai, aqc_sv_t x, double br, double bi);
 /* codes: nterms x n bytes, codes[t*n + q] in {0 I, 1 X, 2 Y, 3 Z} for qubit q; out: nterms doubles
    (batch: nstates x nterms).  The states are sorted to qubit order first, as every measurement.
    <psi|P|psi> is NOT divided by <psi|psi>: same convention as aqc_mps_z_all, so a truncated state
