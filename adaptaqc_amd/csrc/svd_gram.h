@@ -42,9 +42,15 @@ constexpr int kGramNarrowK = 64;  // up to here S5 runs on wave 0 from the LDS a
 //     column pass prefetches column i + 1's LDS operands while column i computes; one row per lane
 //     (two rows per lane measured slower: 0.68 M against 0.64 M ticks)
 // S4: 4 lanes per eigenvalue (5-section), 12 rounds after the first 256-shift pass (8 x 9 x 9 and
-//     16 x 17 x 7 measured 108 K / 145 K against 98 K ticks: the pass is FP64-issue-bound)
+//     16 x 17 x 7 measured 108 K / 145 K against 98 K ticks: the pass is FP64-issue-bound); the
+//     (d, e^2) rows padded so that no read index is clamped, the minors' signs in a history word
+//     with one popcount per 8 rows (67 -> 48 VALU per 8 rows, 99.7 K -> 85.0 K ticks,
+//     profiles/gram_s4s5_phases.json)
 // S5: three inverse-iteration steps per eigenvector; the LDL^T pivots from the leading minors'
-//     recurrence (one FMA + the guard on the chain)
+//     recurrence (one FMA + the guard on the chain); the 8-row chunks read one at a time (two
+//     4-row register sets read a half ahead, from LDS bases laundered once, measured 79.0 K
+//     against 78.3 K ticks for the inverse iteration: no gain, left out); the clusters' join
+//     tests by one ballot, the serial loop over the joined members only (-11 K ticks)
 // S6: the compact-WY factors of every reflector block precomputed during S5 by the idle waves
 //     1-3, 5-7, 9-11 (not 4 and 8, which share SIMD 0 with wave 0's inverse iteration: S5 133 K ->
 //     120 K ticks, k_chain -0.8% against waves 4..11, profiles/r5_s6_skip0_ab.json); W2 = T (Y^H V) on the matrix cores inside the mg == 0 waves; the next block's
@@ -154,21 +160,24 @@ __device__ __forceinline__ int sign_bit(double q) { return (int)((unsigned)__dou
 // (6 dependent FP64 operations per row).  de[i] = (d_i, e_{i-1}^2) pre-scaled by 1 / ||T|| (and
 // x with them), so |p| grows at most 3.1x per row; every 4 rows both minors are rescaled by the
 // larger one's binary exponent (a common positive factor leaves the signs alone), which also
-// keeps runs of tiny pivots from underflowing.  The sign of each minor is its high word shifted
-// arithmetically (0 or -1); the xor of consecutive ones is -1 on a change.
+// keeps runs of tiny pivots from underflowing.  The minors' sign bits are shifted into one history
+// word, newest in bit 0 (one v_alignbit per row); a group of n rows then has its sign changes at
+// the set bits of (h ^ (h >> 1)) below bit n: one popcount per group.
+// de has kSturmPad readable entries past row C - 1 (finite, unused): the loop reads ahead of the
+// rows it uses, at constant offsets from one base, without clamping any index.
+constexpr int kSturmPad = 8;
 __device__ __forceinline__ int sturm_count_poly(const double2* de, int C, double xn) {
   double p0 = 1.0, p1 = de[0].x - xn;
-  int s1 = __double2hiint(p1) >> 31;
-  int neg = s1;  // -(sign changes): p_0 = 1 is positive
+  unsigned int h = (unsigned int)__double2hiint(p1) >> 31;
+  int cnt = (int)h;  // sign changes: p_0 = 1 is positive
   int i = 1;
   auto step = [&](double2 e) {
     const double p2 = fma(e.x - xn, p1, -(e.y * p0));
-    const int s2 = __double2hiint(p2) >> 31;
-    neg += s1 ^ s2;
-    s1 = s2;
+    h = __builtin_amdgcn_alignbit(h, (unsigned int)__double2hiint(p2), 31);  // (h << 1) | sign
     p0 = p1;
     p1 = p2;
   };
+  auto fold = [&](unsigned int mask) { cnt += __popc((h ^ (h >> 1)) & mask); };
   auto rescale = [&]() {
     const int ex = max(__builtin_amdgcn_frexp_exp(p0), __builtin_amdgcn_frexp_exp(p1));
     p0 = __builtin_amdgcn_ldexp(p0, -ex);
@@ -177,9 +186,10 @@ __device__ __forceinline__ int sturm_count_poly(const double2* de, int C, double
   // the next four rows' (d, e^2) are read while the current four run (read and used four at a
   // time, every group of rows waited out an LDS round trip: about half of the pass).  Two named
   // register sets alternate (a rotating copy would wait for its reads at the loop's end); the
-  // index is clamped at the end instead of a branch (the extra reads are unused).
+  // reads past row C - 1 land in the pad and are unused.
   auto rd4 = [&](int i0, double2& r0, double2& r1, double2& r2, double2& r3) {
-    r0 = de[min(i0, C - 1)], r1 = de[min(i0 + 1, C - 1)], r2 = de[min(i0 + 2, C - 1)], r3 = de[min(i0 + 3, C - 1)];
+    const double2* p = de + i0;
+    r0 = p[0], r1 = p[1], r2 = p[2], r3 = p[3];
   };
   double2 a0, a1, a2, a3, b0, b1, b2, b3;
   rd4(1, a0, a1, a2, a3);
@@ -198,17 +208,28 @@ __device__ __forceinline__ int sturm_count_poly(const double2* de, int C, double
     step(b2);
     step(b3);
     rescale();
+    fold(0xFFu);
   }
+  // the last C - i < 8 rows: a group of four (with its rescale) if there is one, then up to three
+  // single rows, all from the two register sets (the second read while the first runs)
+  rd4(i + 4, b0, b1, b2, b3);
+  __builtin_amdgcn_sched_barrier(0);
   if (i + 4 <= C) {
     step(a0);
     step(a1);
     step(a2);
     step(a3);
     rescale();
+    fold(0xFu);
     i += 4;
+    a0 = b0, a1 = b1, a2 = b2;
   }
-  for (; i < C; ++i) step(de[i]);
-  return -neg;
+  const int left = C - i;  // 0 .. 3
+  if (left > 0) step(a0);
+  if (left > 1) step(a1);
+  if (left > 2) step(a2);
+  fold((1u << left) - 1u);
+  return cnt;
 }
 
 __device__ __forceinline__ double rcp_nr(double x) {
@@ -310,13 +331,28 @@ __device__ __forceinline__ void gs_clusters(int K, int C, double* zb, const doub
     for (int row = lane; row < C; row += 64) zb[row * ZS + i] *= sc;
     return n2;
   };
-  int start = 0;
-  for (int i = 1; i < K; ++i) {
+  // The join test of every i in [1, K) at once: lane l tests i = l (and l + 64 where ZS = 128), one
+  // ballot each, and the loop below visits the joined ones only -- none at all on a spectrum without
+  // clusters.  A cluster starts at the last i that did not join: at i - 1 unless i - 1 joined too.
+  auto joins = [&](int i) {
+    if (i < 1 || i >= K) return false;
     const double gap = s_lam[i - 1] - s_lam[i];
-    if (gap >= ortol || (gap >= ortol_any && gap >= 0.05 * s_lam[i - 1])) {
-      start = i;
-      continue;
+    return !(gap >= ortol || (gap >= ortol_any && gap >= 0.05 * s_lam[i - 1]));
+  };
+  static_assert(ZS == 64 || ZS == 128, "one or two ballot words");
+  unsigned long long m0 = __ballot(joins(lane)), m1 = ZS > 64 ? __ballot(joins(lane + 64)) : 0ull;
+  int start = 0, prev = 0;
+  while (m0 | m1) {  // (uniform) the joined i in ascending order
+    int i;
+    if (m0) {
+      i = __builtin_ctzll(m0);
+      m0 &= m0 - 1;
+    } else {
+      i = 64 + __builtin_ctzll(m1);
+      m1 &= m1 - 1;
     }
+    if (i - 1 != prev) start = i - 1;
+    prev = i;
     for (int again = 0;; ++again) {  // (uniform: every value below is a wave sum)
       for (int jj = start; jj < i; ++jj) {
         double dp = 0.0;
@@ -954,7 +990,7 @@ int gram_svd_body(const TwoSiteJob& j, int epi) {
   __shared__ int s_K, s_cert, s_fk;
   __shared__ cplx s_tau[128];
   __shared__ double s_lo, s_hi, s_tn;
-  __shared__ double2 s_de[128];
+  __shared__ double2 s_de[128 + kSturmPad];
   const int chl = j.dims[0], chr = j.dims[2];
   const int M = 2 * chl, N = 2 * chr;
   const bool tr = M < N;
@@ -1403,6 +1439,7 @@ int gram_svd_body(const TwoSiteJob& j, int epi) {
       const double2 de = s_de[i];
       s_de[i] = make_double2(de.x * itn, de.y * itn * itn);
     }
+    if (lane < kSturmPad) s_de[C + lane] = make_double2(0.0, 0.0);  // (read ahead, never used)
   }
   __syncthreads();
   {
@@ -1458,6 +1495,22 @@ int gram_svd_body(const TwoSiteJob& j, int epi) {
   }
   __syncthreads();
   if (tid == 0) s_K = aqc::gram_keep(s_lam, s_err, KE, C, j.max_chi, j.thr, s_tn, kGramRelFloor, s_tail, &s_cert);
+  if (wave != 0) {
+    // S5's deterministic start vectors, in [-1, 1): a hash of (row, i) alone, written by the 15 waves
+    // that wait for thread 0's gram_keep (by wave 0 after it, its 128 serial rows were 7 K ticks of
+    // the inverse iteration).  K is not known yet: all min(KE, 64) columns the narrow path can keep
+    // (the wide path writes its own).  S4's counts in the first 1 KB here are dead since the barrier.
+    double* zs = reinterpret_cast<double*>(xbuf);  // zb[row * 64 + i] below
+    const int i = lane;
+    if (i < KE)
+      for (int row = wave - 1; row < C; row += 15) {
+        unsigned int h = (unsigned int)(row * 2654435761u) ^ (unsigned int)((i + 1) * 40503u);
+        h ^= h >> 13;
+        h *= 0x5bd1e995u;
+        h ^= h >> 15;
+        zs[row * 64 + i] = (double)(h & 0xFFFFFu) * (2.0 / 1048576.0) - 1.0;
+      }
+  }
   __syncthreads();
   tick(2);
   const int K = s_K;  // (uniform)
@@ -1476,13 +1529,7 @@ int gram_svd_body(const TwoSiteJob& j, int epi) {
     const int i = tid;
     const double lam = s_lam[i];
     const double piv = 2.220446049250313e-16 * s_tn;
-    for (int row = 0; row < C; ++row) {  // deterministic start vector, in [-1, 1)
-      unsigned int h = (unsigned int)(row * 2654435761u) ^ (unsigned int)((i + 1) * 40503u);
-      h ^= h >> 13;
-      h *= 0x5bd1e995u;
-      h ^= h >> 15;
-      zb[row * 64 + i] = (double)(h & 0xFFFFFu) * (2.0 / 1048576.0) - 1.0;
-    }
+    // (the start vector is in zb already: written by the other waves beside gram_keep)
     // L D L^T = T - lam I once (no pivoting; tiny pivots -> +-eps ||T||): 1 / D_row to Db.  The
     // recurrences below are serial per lane: T's entries and the vectors' rows are loaded eight
     // rows ahead of the dependent chain (read one at a time, every step waited out an LDS round
