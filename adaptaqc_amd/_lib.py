@@ -61,6 +61,8 @@ EXPORTS = (
     "aqc_dm_diag_sv", "aqc_dm_pauli_expect", "aqc_dm_pair_rdms",
     "aqc_dm_apply_adjoint", "aqc_dm_plan_adjoint", "aqc_dm_set", "aqc_dm_set_diag", "aqc_dm_copy", "aqc_dm_transition",
     "aqc_dm_pair_envs", "aqc_dm_pair_transitions", "aqc_dm_pair_transitions_plan",
+    "aqc_mps_dmrg_plan", "aqc_dmrg_create", "aqc_dmrg_sweep", "aqc_dmrg_destroy", "aqc_dmrg_heff_apply",
+    "aqc_dmrg_stats",
 )
 
 
@@ -210,6 +212,12 @@ _SIGS = {
     "aqc_dm_pair_envs": ([_P, _P, _I, _P, _P], _I),
     "aqc_dm_pair_transitions": ([_P, _P, _P, _I, _P], _I),
     "aqc_dm_pair_transitions_plan": ([_I, _I, _IP], _I),
+    "aqc_mps_dmrg_plan": ([_I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P], _I),
+    "aqc_dmrg_create": ([_P, _P, _P, _I, _I, ctypes.POINTER(_P)], _I),
+    "aqc_dmrg_sweep": ([_P, _P], _I),
+    "aqc_dmrg_destroy": ([_P], _I),
+    "aqc_dmrg_heff_apply": ([_P, _I, _P, _P], _I),
+    "aqc_dmrg_stats": ([_P, _P], _I),
 }
 
 

@@ -1738,14 +1738,16 @@ KrausJob make_kraus(aqc_mps_t h, const DevOp& op, int shot) {
 
 }  // namespace
 
-int aqc::run_waves(aqc_mps_t* hs, int ns, std::vector<std::vector<DevOp>>& lists, const TrajCtx* ctx) {
-  bool kraus = false;
+int aqc::run_waves(aqc_mps_t* hs, int ns, std::vector<std::vector<DevOp>>& lists, const TrajCtx* ctx,
+                   aqc_dmrg_s* dmrg) {
+  bool kraus = false, dm = false;
   for (int s = 0; s < ns; ++s) {  // every Gamma these lists write (reload bookkeeping)
     int lo = 1 << 30, hi = -1;
     for (const DevOp& op : lists[s]) {
       lo = std::min(lo, op.kind == 5 ? std::min(op.p, op.p2) : op.p);
       hi = std::max(hi, aqc::two_site(op) ? op.p + 1 : op.kind == 5 ? std::max(op.p, op.p2) : op.p);
-      kraus |= op.kind >= 3;
+      kraus |= op.kind >= 3 && op.kind != 6;
+      dm |= op.kind == 6;
     }
     if (hi >= 0) hs[s]->changed(lo, hi);
   }
@@ -1753,7 +1755,11 @@ int aqc::run_waves(aqc_mps_t* hs, int ns, std::vector<std::vector<DevOp>>& lists
     aqc::set_error("run_waves: Kraus rows without a trajectory context");
     return AQC_ERR_ARG;
   }
-  if (!kraus) {  // (k_chain has no Kraus phase: such lists run in lock-step whatever the batch)
+  if (dm && !(dmrg && ns == 1)) {
+    aqc::set_error("run_waves: DMRG updates need their handle and a single state");
+    return AQC_ERR_ARG;
+  }
+  if (!kraus && !dm) {  // (k_chain has no Kraus phase: such lists run in lock-step whatever the batch)
     int cap_max = 0;
     for (int s = 0; s < ns; ++s) cap_max = std::max(cap_max, hs[s]->d.cap);
     if (g_fused_chain && ns >= g_chain_min_states && 2 * cap_max > 64 && 2 * cap_max <= 128)
@@ -1807,6 +1813,7 @@ int aqc::run_waves(aqc_mps_t* hs, int ns, std::vector<std::vector<DevOp>>& lists
   std::vector<std::pair<int, TwoSiteJob>> wjobs;
   std::vector<int> wev;  // per wave job: -1, or the general event (index into k2) that acts on its theta
   std::vector<size_t> idx;
+  std::vector<const DevOp*> dm_op(maxlen, nullptr);  // the wave's DMRG update (one state: at most one a wave)
   for (size_t w = 0; w < maxlen; ++w) {
     size_t t0 = two.size(), o0 = one.size(), k0 = kr.size(), e0 = k2.size(), p0 = kp.size();
     wjobs.clear();
@@ -1821,6 +1828,7 @@ int aqc::run_waves(aqc_mps_t* hs, int ns, std::vector<std::vector<DevOp>>& lists
           const int cls = class_of(2 * std::max(ub[p], ub[p + 2]));
           wjobs.push_back({cls, make_two(hs[s], *op, slot++)});
           wev.push_back(op->kind == 4 ? (int)k2.size() : -1);
+          if (op->kind == 6) dm_op[w] = op;
           if (op->kind == 4) k2.push_back({0, op->grp, op->slot, ctx->shot0 + s});
           wjobs.back().second.qr = cls <= 128 ? 1 : 0;
           int nb = std::min(2 * std::min(ub[p], ub[p + 2]), hs[s]->d.cap);
@@ -1930,6 +1938,9 @@ int aqc::run_waves(aqc_mps_t* hs, int ns, std::vector<std::vector<DevOp>>& lists
       // applied to it in place, and the wave's SVD and split then serve it like any other job
       if (k2_rng[w].second)
         if (int e = aqc::launch_kraus2(jp, dk2 + k2_rng[w].first, (int)k2_rng[w].second, cap_max, *ctx, st)) return e;
+      // a DMRG update: the lowest Ritz vector of the bond's effective Hamiltonian replaces theta
+      if (dm_op[w])
+        if (int e = aqc::launch_heff(*dm_op[w], dmrg, st)) return e;
       aqc::KernelTimer::begin(st, "mps_svd", nj * 2.0 * (4.0 * c * c * 16), 0.0);
       for (const ClassRange& cr : wave_cls[w]) {
         const int side = cr.cls, nc = (int)cr.count;
@@ -1960,6 +1971,8 @@ int aqc::run_waves(aqc_mps_t* hs, int ns, std::vector<std::vector<DevOp>>& lists
       hipLaunchKernelGGL(k_split_gemm, dim3(aqc::xcd_grid(blocks_split, nj)), dim3(aqc::kGemmThreads), 0, st, jp, nj);
       aqc::KernelTimer::end(st);
       AQC_CHECK_LAUNCH();
+      if (dm_op[w])
+        if (int e = aqc::launch_dmrg_env(*dm_op[w], dmrg, st)) return e;
     }
   }
   return AQC_OK;  // the lease records the set's event

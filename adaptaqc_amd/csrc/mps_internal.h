@@ -8,6 +8,8 @@
 
 #include "aqc_internal.h"
 
+struct aqc_dmrg_s;  // dmrg.hip
+
 namespace aqc {
 
 // Device layout of one MPS (Vidal form, as Aer's MPS simulator keeps it):
@@ -326,7 +328,10 @@ class StagingLease {
 struct DevOp {
   // 1: one-site, 2: two-site (p, p+1), 3: one-site Kraus / measurement row, 4: a correlated group's
   // event as a two-site update of (p, p+1) whose 4x4 operator is chosen on the device, 5: a
-  // product-unitary group's event on the sites p and p2 (any two; mps_traj.hip)
+  // product-unitary group's event on the sites p and p2 (any two; mps_traj.hip), 6: a DMRG update of
+  // (p, p+1): theta is formed with the identity and a Lanczos iteration on the bond's effective
+  // Hamiltonian replaces it with the lowest Ritz vector (dmrg.hip); slot = the sweep's output slot of
+  // the Ritz value, grp = the direction (0: left to right)
   int kind;
   int p;
   cplx m[16];  // kind 3: the nk 2x2 operators K_k, 4 elements each; kind 4: the identity (theta's G)
@@ -338,7 +343,7 @@ struct DevOp {
 };
 
 // the rows that run as two-site updates of (p, p+1)
-inline bool two_site(const DevOp& d) { return d.kind == 2 || d.kind == 4; }
+inline bool two_site(const DevOp& d) { return d.kind == 2 || d.kind == 4 || d.kind == 6; }
 
 // host complex arithmetic without fma(): the x86 host build has no FMA instructions enabled, so
 // fma() is a libm call per operation
@@ -543,9 +548,18 @@ int launch_kraus2(const TwoSiteJob* two, const Kraus2Job* jobs, int nj, int cap_
 // Queues k_mps_kraus2_prod over nj device jobs on st (mps_traj.hip).
 int launch_kraus2_prod(const Kraus2ProdJob* jobs, int nj, int cap_max, const TrajCtx& ctx, hipStream_t st);
 
+// Queues a kind-6 op's eigensolver on st, behind the k_theta launch that formed its theta (G = identity)
+// and in front of the wave's SVD: the lowest Ritz vector of the bond's effective Hamiltonian over theta,
+// normalised, the Ritz value to the sweep's slot (dmrg.hip).
+int launch_heff(const DevOp& op, aqc_dmrg_s* dmrg, hipStream_t st);
+// Queues, behind the op's split, the environment step through the site the update has just fixed.
+int launch_dmrg_env(const DevOp& op, aqc_dmrg_s* dmrg, hipStream_t st);
+
 // Runs per-state device-op lists in lock-step waves on the MPS stream (mps.hip); returns once the
-// work is queued.  Lists with kind-3 rows need ctx and never take the fused chain.
-int run_waves(aqc_mps_s** hs, int ns, std::vector<std::vector<DevOp>>& lists, const TrajCtx* ctx = nullptr);
+// work is queued.  Lists with kind-3 rows need ctx and never take the fused chain.  Kind-6 ops need
+// dmrg, one state, and never take the fused chain either.
+int run_waves(aqc_mps_s** hs, int ns, std::vector<std::vector<DevOp>>& lists, const TrajCtx* ctx = nullptr,
+              aqc_dmrg_s* dmrg = nullptr);
 
 // The handle back to |0...0> in sorted qubit order, queued on the MPS stream (mps.hip).
 int mps_reset_zero(aqc_mps_s* h);

@@ -500,6 +500,105 @@ class DeviceMPS:
         return out.reshape(-1, 4, 4)
 
 
+def _dmrg_operator(operator, n):
+    """(codes (nterms, n) uint8, real coefficients float64) of a Pauli sum in the forms
+    ``DeviceSV.pauli_apply`` takes; a Hamiltonian's coefficients are real."""
+    from . import paulis
+
+    if isinstance(operator, dict):
+        terms, coeffs = list(operator.keys()), list(operator.values())
+    else:
+        terms, coeffs = operator
+    codes = paulis.terms_to_codes(terms, n)
+    coeffs = np.asarray(coeffs, dtype=np.complex128).reshape(-1)
+    if len(coeffs) != len(codes):
+        raise ValueError(f"a Pauli sum needs one coefficient per term: {len(codes)} terms, {len(coeffs)} coefficients")
+    if np.any(coeffs.imag != 0):
+        raise ValueError("a Hamiltonian (a Hermitian Pauli sum) has real coefficients")
+    return codes, np.ascontiguousarray(coeffs.real, dtype=np.float64)
+
+
+DMRG_CLASSES = ("closed left", "closed right", "local", "open", "identity")
+DMRG_RECORD_KINDS = ("LH", "RH", "local", "open")
+
+
+def dmrg_plan(n, operator, chi_cap=64, krylov_dim=6):
+    """The bond plan of a two-site DMRG of ``operator`` on n qubits (aqc_mps_dmrg_plan; no GPU): a dict
+    with the totals (``total_records``, ``max_records``, ``env_matrices``, ``env_bytes`` and
+    ``scratch_bytes`` at ``chi_cap``, ``record_limit``, ``byte_budget``, ``identities``), ``bonds`` (per
+    bond: records, closed-left, closed-right and local terms, open records, stored left and right
+    environments of open terms), ``records`` (rows of bond, kind, term, flags; kinds ``DMRG_RECORD_KINDS``,
+    flag bit 0 / 1: a stored left / right environment) and ``classes`` ((n - 1, nterms), indices into
+    ``DMRG_CLASSES``).  Raises ``AqcError`` naming the numbers when a bond has more records than the
+    limit or environments and scratch exceed the byte budget."""
+    n = int(n)
+    if n < 1:
+        raise ValueError("dmrg_plan: n >= 1")
+    codes, coeffs = _dmrg_operator(operator, n)
+    l = _lib.load()
+    totals = np.zeros(8, dtype=np.int64)
+    bonds = np.zeros((max(n - 1, 0), 7), dtype=np.int32)
+    classes = np.zeros((max(n - 1, 0), len(codes)), dtype=np.uint8)
+    args = (n, _lib.ptr(codes), _lib.ptr(coeffs), len(codes), int(chi_cap), int(krylov_dim), _lib.ptr(totals))
+    _lib.check(l.aqc_mps_dmrg_plan(*args, _lib.ptr(bonds), None, 0, _lib.ptr(classes)))
+    records = np.zeros((int(totals[0]), 4), dtype=np.int32)
+    _lib.check(l.aqc_mps_dmrg_plan(*args, None, _lib.ptr(records) if len(records) else None, len(records), None))
+    names = ("total_records", "max_records", "env_matrices", "env_bytes", "scratch_bytes", "record_limit", "byte_budget",
+             "identities")
+    out = {k: int(v) for k, v in zip(names, totals)}
+    out.update(bonds=bonds, records=records, classes=classes)
+    return out
+
+
+class DeviceDMRG:
+    """Two-site DMRG of a Pauli sum on a ``DeviceMPS`` (aqc_dmrg_*): the environments, the Krylov scratch
+    and the record tables.  The MPS is not owned and must outlive the handle; after any change of it that
+    is not one of this handle's sweeps, every call is refused."""
+
+    def __init__(self, mps, operator, krylov_dim=6):
+        self._l = _lib.lib()
+        self.mps = mps
+        self.n = mps.n
+        codes, coeffs = _dmrg_operator(operator, self.n)
+        h = ctypes.c_void_p()
+        _lib.check(self._l.aqc_dmrg_create(mps.h, _lib.ptr(codes), _lib.ptr(coeffs), len(codes), int(krylov_dim),
+                                           ctypes.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None) is not None and self.h.value:
+            self._l.aqc_dmrg_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def sweep(self):
+        """One sweep (left to right, then back): the 2 (n - 1) Ritz values in update order."""
+        out = np.zeros(2 * (self.n - 1))
+        _lib.check(self._l.aqc_dmrg_sweep(self.h, _lib.ptr(out)))
+        return out
+
+    def heff_apply(self, bond, x):
+        """y = H_eff x at ``bond`` with the environments of the state as it stands (test hook,
+        aqc_dmrg_heff_apply); x in theta's layout, 4 dims[bond] dims[bond + 2] complex numbers."""
+        bond = int(bond)
+        d = self.mps.dims()
+        if not 0 <= bond < self.n - 1:
+            raise ValueError("heff_apply: bond outside 0 .. n - 2")
+        x = np.ascontiguousarray(x, dtype=np.complex128).reshape(-1)
+        if len(x) != 4 * int(d[bond]) * int(d[bond + 2]):
+            raise ValueError(f"heff_apply: x needs {4 * int(d[bond]) * int(d[bond + 2])} amplitudes, got {len(x)}")
+        y = np.zeros_like(x)
+        _lib.check(self._l.aqc_dmrg_heff_apply(self.h, bond, _lib.ptr(x), _lib.ptr(y)))
+        return y
+
+    def stats(self):
+        """{"breakdowns": bond updates whose Lanczos iteration ended early, "updates": bond updates}."""
+        out = np.zeros(2, dtype=np.int64)
+        _lib.check(self._l.aqc_dmrg_stats(self.h, _lib.ptr(out)))
+        return {"breakdowns": int(out[0]), "updates": int(out[1])}
+
+
 def _u64(x):
     return ctypes.c_uint64(int(x) & 0xFFFFFFFFFFFFFFFF)
 

@@ -23,6 +23,10 @@ OpenFermion's Jordan-Wigner transform and is not provided.
 ``calculate_ground_state`` (hamiltonians.py:80-85, there OpenFermion's sparse eigensolver on the
 host) is a Lanczos iteration on device statevectors: the operator apply, the inner products and
 the vector updates are libaqchip kernels (csrc/sv_linalg.hip); the host holds the tridiagonal.
+
+``calculate_ground_state_mps`` has no counterpart in the reference: above a statevector's reach the ground
+state is found as a matrix-product state by two-site DMRG on the MPS engine (csrc/dmrg.hip), and returned
+in the Aer format the compiler takes as a target.
 """
 import math
 from dataclasses import dataclass
@@ -192,4 +196,140 @@ def calculate_ground_state(hamiltonian, tol=1e-9, max_iterations=300, max_restar
         return energy, psi
     out = psi.get()
     psi.close()
+    return energy, out
+
+
+# ---- matrix-product ground states: two-site DMRG on the MPS engine --------------------------------------
+@dataclass
+class GroundStateMPSRun:
+    """What the last ``calculate_ground_state_mps`` call did (``last_run_mps``)."""
+    energy: float      # sum_t c_t <P_t> of the returned state
+    energies: list     # the same after every sweep
+    sweeps: int
+    max_bond: int      # the largest bond dimension of the returned state
+    scale: float       # S = sum_t |c_t|; the call converged to |E - E_prev| <= tol * S
+    variance: float    # sigma^2 = <H^2> - E^2, resolved to about 1e-11 S^2 (see calculate_ground_state_mps)
+    breakdowns: int    # bond updates whose Lanczos iteration ended early (aqc_dmrg_stats)
+    updates: int       # bond updates
+
+
+last_run_mps = None
+
+
+def _squared_operator(codes, coeffs):
+    """H^2 of H = sum_t c_t P_t as (codes, real coefficients), its label products formed on the host:
+    with P = i^{|x & z|} X^x Z^z, P_a P_b = i^{ny_a + ny_b - ny_ab} (-1)^{|z_a & x_b|} P_ab.  Products of
+    the same string are added; the anticommuting pairs cancel, and what is left is real."""
+    x = (codes == 1) | (codes == 2)
+    z = (codes == 3) | (codes == 2)
+    ny = np.sum(x & z, axis=1)
+    total = {}
+    for a in range(len(codes)):
+        xa = x[a][None, :] ^ x
+        za = z[a][None, :] ^ z
+        k = (ny[a] + ny - np.sum(xa & za, axis=1) + 2 * np.sum(z[a][None, :] & x, axis=1)) % 4
+        prod = np.where(xa & za, 2, np.where(xa, 1, np.where(za, 3, 0))).astype(np.uint8)
+        w = coeffs[a] * coeffs * np.array([1, 1j, -1, -1j])[k]
+        for b in range(len(codes)):
+            key = prod[b].tobytes()
+            total[key] = total.get(key, 0.0) + w[b]
+    keys = [k for k, v in total.items() if v.real != 0.0]
+    out = np.frombuffer(b"".join(keys), dtype=np.uint8).reshape(len(keys), codes.shape[1])
+    return np.ascontiguousarray(out), np.array([total[k].real for k in keys])
+
+
+def calculate_ground_state_mps(hamiltonian, max_chi=64, threshold=1e-16, tol=1e-9, max_sweeps=30, krylov_dim=6, seed=0,
+                               initial_circuit=None, initial_mps=None, return_device=False):
+    """``(energy, mps)``: the ground state of a ``{label: real coefficient}`` Hamiltonian as a
+    matrix-product state, by two-site DMRG (density-matrix renormalisation group) on the MPS engine --
+    ``calculate_ground_state`` beyond a statevector's reach.  ``mps`` is the Aer-format MPS
+    (``DeviceMPS.to_aer()``) that ``AdaptCompiler(target=...)`` takes directly; with ``return_device`` it is
+    the ``DeviceMPS`` that holds it.
+
+    The start state is, by default, a product state with ``ry`` / ``rz`` angles drawn from ``seed`` on every
+    qubit -- it has weight in every S_z sector, and a two-site update cannot leave a symmetry sector that
+    the start lacks; otherwise ``initial_circuit`` run on the engine, or the Aer-format ``initial_mps``.
+    A sweep updates the bonds 0 .. n - 2 left to right, then back (``DeviceDMRG.sweep``): each update is a
+    Lanczos iteration of ``krylov_dim`` steps on the bond's effective Hamiltonian and the engine's SVD
+    with the truncation (``max_chi``, ``threshold``).  After every sweep the energy is the state's own,
+    E = sum_t c_t <P_t> from ``pauli_expect`` (truncation moves it off the last Ritz value), and the call
+    stops at |E - E_prev| <= tol S, S = sum_t |c_t|.  If that has not happened after ``max_sweeps`` the call
+    raises ``RuntimeError`` naming the last change: an unconverged state is never returned.
+
+    ``last_run_mps`` keeps the energies, the sweeps, the largest bond and the variance sigma^2 = <H^2> - E^2
+    (the label products of H^2 formed on the host, read by one ``pauli_expect`` call).  sigma^2 is resolved
+    only to about 1e-11 S^2 -- the per-term accuracy of the MPS Pauli reader times sum |c_a c_b| -- so it is
+    a report, not a stopping rule.  Labels are limited to 64 qubits by ``_checked_hamiltonian``."""
+    global last_run_mps
+    n, _, _, c, scale = _checked_hamiltonian(hamiltonian)
+    if n < 2:
+        raise ValueError("calculate_ground_state_mps: a two-site update needs at least 2 qubits")
+    tol, max_sweeps, max_chi, krylov_dim = float(tol), int(max_sweeps), int(max_chi), int(krylov_dim)
+    if not tol > 0 or max_sweeps < 1 or max_chi < 1 or not float(threshold) >= 0:
+        raise ValueError("calculate_ground_state_mps: tol > 0, max_sweeps >= 1, max_chi >= 1 and threshold >= 0")
+    if not 2 <= krylov_dim <= 16:
+        raise ValueError("calculate_ground_state_mps: krylov_dim must be in 2 .. 16")
+    if initial_circuit is not None and initial_mps is not None:
+        raise ValueError("calculate_ground_state_mps: give initial_circuit or initial_mps, not both")
+    from .. import paulis
+    from ..device import DeviceDMRG, DeviceMPS
+
+    labels = list(hamiltonian.keys())
+    coeffs = c.real.copy()
+    codes = paulis.terms_to_codes(labels, n)
+    cap = min(max_chi, 1 << (n // 2), 1024)
+    if initial_mps is not None:
+        gam, _ = initial_mps
+        if len(gam) != n:
+            raise ValueError(f"calculate_ground_state_mps: initial_mps has {len(gam)} sites for {n} qubits")
+        cap = max(cap, max(int(np.asarray(g[0]).shape[1]) for g in gam))
+    mps = DeviceMPS(n, cap, float(threshold), max_chi)
+    try:
+        if initial_mps is not None:
+            mps.load_aer(initial_mps)
+        elif initial_circuit is not None:
+            from ..circuit import device_ops
+
+            if initial_circuit.num_qubits != n:
+                raise ValueError(f"calculate_ground_state_mps: initial_circuit has {initial_circuit.num_qubits} qubits for {n}")
+            mps.apply(device_ops(initial_circuit))
+        else:
+            rng = np.random.default_rng(seed)
+            ops = []
+            for q in range(n):
+                t, p = rng.uniform(0.0, math.pi), rng.uniform(0.0, 2.0 * math.pi)
+                ry = np.array([[math.cos(t / 2), -math.sin(t / 2)], [math.sin(t / 2), math.cos(t / 2)]], dtype=complex)
+                rz = np.diag([np.exp(-0.5j * p), np.exp(0.5j * p)])
+                ops.append((rz @ ry, (q,)))
+            mps.apply(ops)
+        dm = DeviceDMRG(mps, (codes, coeffs), krylov_dim)
+        try:
+            energies = []
+            change = math.inf
+            for _ in range(max_sweeps):
+                dm.sweep()
+                energies.append(float(np.dot(coeffs, mps.pauli_expect(codes))))
+                if len(energies) > 1:
+                    change = abs(energies[-1] - energies[-2])
+                    if change <= tol * scale:
+                        break
+            energy = energies[-1]
+            sq_codes, sq_coeffs = _squared_operator(codes, coeffs)
+            variance = float(np.dot(sq_coeffs, mps.pauli_expect(sq_codes))) - energy * energy
+            stats = dm.stats()
+        finally:
+            dm.close()
+        last_run_mps = GroundStateMPSRun(energy=energy, energies=energies, sweeps=len(energies),
+                                         max_bond=int(mps.dims().max()), scale=scale, variance=variance,
+                                         breakdowns=stats["breakdowns"], updates=stats["updates"])
+        if not change <= tol * scale:
+            raise RuntimeError(f"calculate_ground_state_mps: the energy still changed by {change:.3e}, above tol * S = "
+                               f"{tol * scale:.3e}, in the last of {max_sweeps} sweeps")
+    except BaseException:
+        mps.close()
+        raise
+    if return_device:
+        return energy, mps
+    out = mps.to_aer()
+    mps.close()
     return energy, out

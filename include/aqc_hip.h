@@ -539,6 +539,45 @@ int aqc_sv_axpby(aqc_sv_t y, double ar, double ai, aqc_sv_t x, double br, double
 int aqc_mps_pauli_expect(aqc_mps_t h, const uint8_t* codes, int nterms, double* out);
 int aqc_mps_pauli_expect_batch(aqc_mps_t* hs, int nstates, const uint8_t* codes, int nterms, double* out);
 
+/* ---- two-site DMRG ground states of a Pauli sum on the MPS engine (dmrg.hip): the route of
+   calculate_ground_state above a statevector's reach ------------------------------------------------
+   H = sum_t c_t P_t with real c_t; codes as aqc_mps_pauli_expect takes them.  At bond b (sites b, b + 1,
+   0 <= b <= n - 2) a term with support lo..hi is closed left (hi < b: summed into one matrix LH_b),
+   closed right (lo > b + 1: into RH_b), local (b <= lo, hi <= b + 1: into one 4 x 4 matrix h_b), open
+   (anything else: a record of its own) or, without support, a constant kept on the host.
+   aqc_mps_dmrg_plan needs no GPU.  totals[8]: records over all bonds, the most records of one bond,
+   stored environment matrices, their bytes at chi_cap, the bytes of scratch (W of every record, the
+   Krylov basis, the environment steps' panels), the record limit of one bond, the byte budget of
+   environments plus scratch, the number of identity terms.  bonds (null, or (n - 1) x 7): records, closed
+   left terms, closed right terms, local terms, open records, stored left environments of open terms,
+   stored right ones.  records (null, or records_cap >= totals[0] rows of 4): bond, kind (0 LH, 1 RH,
+   2 local, 3 open), term (kind 3, else -1), flags (bit 0: a stored left environment, bit 1: a stored
+   right one); a bond's records in the order LH, RH, local, then its open terms in input order.  classes
+   (null, or (n - 1) x nterms bytes): 0 closed left, 1 closed right, 2 local, 3 open, 4 identity.
+   AQC_ERR_ARG: n outside 2 .. 4096, nterms outside 1 .. 2^20, chi_cap outside 1 .. 1024, krylov_dim outside
+   2 .. 16, a code above 3, a coefficient that is not finite, a bond with more records than the limit,
+   environments plus scratch above the budget (the last two name their numbers). */
+typedef struct aqc_dmrg_s* aqc_dmrg_t;
+int aqc_mps_dmrg_plan(int n, const uint8_t* codes, const double* coeffs, int nterms, int chi_cap, int krylov_dim,
+                      int64_t* totals, int* bonds, int* records, int records_cap, uint8_t* classes);
+/* A DMRG handle on `mps` (which it does not own and which must outlive it): the environments, the Krylov
+   scratch and the record tables at the state's capacity.  AQC_ERR_ARG as the plan; the MPS is not
+   touched.  The handle follows the state through its own sweeps and refuses it (AQC_ERR_STATE) after any
+   other change. */
+int aqc_dmrg_create(aqc_mps_t mps, const uint8_t* codes, const double* coeffs, int nterms, int krylov_dim,
+                    aqc_dmrg_t* out);
+/* One sweep: two-site updates of the bonds 0 .. n - 2 left to right, then back.  An update forms theta,
+   replaces it with the lowest Ritz vector of a Lanczos iteration of krylov_dim steps (full
+   reorthogonalisation; every scalar on the device; ended early at beta <= 256 eps S, S = sum |c_t|, or
+   when the space is exhausted) on the bond's effective Hamiltonian, and hands it to the engine's SVD,
+   truncation (the state's max_chi and threshold), renormalisation and split; the environment step
+   for the next bond follows.  The first sweep first sorts the qubits and runs identity updates in both
+   directions (the gauge), then builds every right environment.  Nothing waits on the host between
+   bonds.  bond_energies: 2 (n - 1) Ritz values in update order.  Every sum runs in a fixed order: the
+   same state and operator give the same bits. */
+int aqc_dmrg_sweep(aqc_dmrg_t h, double* bond_energies);
+int aqc_dmrg_destroy(aqc_dmrg_t h);
+
 /* ---- shot-based pair tomography: replaces the per-pair circuits of entanglement_measures.py:101-135
    (perform_quantum_tomography) and :138-250 (measure_concurrence_lower_bound) ----
    Each of those circuits measures two qubits, so its counts are a multinomial draw that the pair's

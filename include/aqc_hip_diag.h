@@ -146,6 +146,16 @@ int aqc_sweep_set_chain_mode(int mode);
    out[shot * nper + site], generated on the device and copied to the host (tests pin the generator
    with it). */
 int aqc_sample_uniforms(uint64_t seed, uint64_t run, int nshots, int nper, double* out);
+/* Test hook of the DMRG kernels: builds the environments of `bond` from the handle's state as it stands
+   (every left step up to the bond, every right step down to it) and applies the bond's effective
+   Hamiltonian once, y = H_eff x.  x, y: 4 chi_l chi_r complex numbers in theta's layout,
+   [(s2 chi_r + r) 2 chi_l + s1 chi_l + l], chi_l = dims[bond], chi_r = dims[bond + 2]; the identity
+   terms' constant is not part of H_eff.  The state is not changed.  AQC_ERR_STATE for a state that is
+   not in sorted qubit order or was changed outside the handle. */
+int aqc_dmrg_heff_apply(aqc_dmrg_t h, int bond, const double* x, double* y);
+/* Counters of a DMRG handle since its creation: out[0] bond updates whose Lanczos iteration ended on a
+   breakdown, out[1] bond updates. */
+int aqc_dmrg_stats(aqc_dmrg_t h, int64_t* out);
 #ifdef __cplusplus
 }
 #endif
